@@ -11,15 +11,21 @@ A "step" is one pass of the hot path over one batch of synthetic candidates resi
 
 followed, for N > 1 GPUs, by ONE RCCL all-gather of the per-rank (value, index) winners, a merge kernel and one
 16-byte device-to-host copy.  `update` (K assembly + Cholesky + inverse) is outside the timed region and reported in
-`config`.
+`config` by `--full`.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|c2|c3|c4|c5]
-                    [--scaling weak|strong] [--mode ranks|group]
+                    [--scaling weak|strong] [--mode ranks|group] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no torch.distributed environment re-launches itself as N ranks (one process per GPU,
 `python -m torch.distributed.run --nproc-per-node N ...`, backend nccl = RCCL); under torchrun it is one of the ranks.
 `--mode group` instead drives all N GPUs from ONE process through the C-ABI's single-controller group
 (tgp_group_*: in-process RCCL communicator).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line used
+to carry: `update_ms` (median of five updates), the end-to-end acquire / fit / small-call timings, the secondary
+workloads attached to the f64 headline and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+returned (the winning values and global indices; the qEI values of every q-batch on the qei workload) as float64
+`DIR/<name>.npy` files.
 """
 from __future__ import annotations
 
@@ -361,6 +367,25 @@ def respawn_as_ranks(n: int) -> None:
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """Write each output as float64 ``path/<name>.npy`` (indices are exact in float64 below 2^53).  An array that would
+    push the total past 64 MB is replaced by a fixed, seeded sample of its elements, stored with their flat indices
+    (``<name>_sample_index.npy``), so that two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in outputs.items()}
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if a.nbytes > budget:
+            keep = budget // (2 * a.itemsize)
+            idx = np.sort(np.random.default_rng(20240916).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(path, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -373,11 +398,18 @@ def main():
                     help="ranks: one process per GPU over torch.distributed/RCCL; group: one process, tgp_group_*")
     ap.add_argument("--merge", default="rccl", choices=("rccl", "peer"), help="group mode: winner exchange")
     ap.add_argument("--m-per-gpu", type=int, default=0, help="override the units per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: update_ms, the end-to-end acquire / fit / "
+                         "small-call timings, the secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary workloads (c2 / c4 / c5 / emulated i8x5 headline) attached to the default line")
+                    help="with --full: skip the secondary workloads (c2 / c4 / c5 / emulated i8x5 headline) attached to "
+                         "the default line")
     ap.add_argument("--secondary-steps", type=int, default=3)
-    ap.add_argument("--no-acquire", action="store_true", help="skip the informational end-to-end acquire timing")
+    ap.add_argument("--no-acquire", action="store_true",
+                    help="with --full: skip the informational end-to-end acquire / fit / small-call timings")
     ap.add_argument("--variant", type=int, default=0, help="tgp_set_variant launch-policy bits (experiments)")
     ap.add_argument("--precision", default="f64", choices=("f64", "i8x4", "i8x5", "auto"),
                     help="arithmetic of the EI sweeps: f64 (default, the parity path) or i8x4 = W K* on the int8 matrix "
@@ -385,6 +417,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.mode == "ranks" and args.gpus > 1 and not under_launcher:
@@ -434,6 +468,8 @@ def main():
     X, Y = O.synthetic_problem(getattr(O, w["objective"]), d, N)  # seed 1234, standardised
     ls = O.default_lengthscales(d)
     dev = f"cuda:{local_rank}"
+    last = {}  # what the latest step returned to its caller (--dump-outputs)
+    update_ms = None
 
     if group_mode:
         from trieste_amd.group import GPEngineGroup
@@ -448,9 +484,10 @@ def main():
             m.set_precision(args.precision)
         grp.set_hyper(1.0, ls, noise, float(Y.mean()))
         grp.set_data(X, Y)  # warm-up (allocations)
-        t0 = time.perf_counter()
-        grp.set_data(X, Y)  # every member runs the same deterministic update, concurrently
-        update_ms = (time.perf_counter() - t0) * 1e3
+        if args.full:
+            t0 = time.perf_counter()
+            grp.set_data(X, Y)  # every member runs the same deterministic update, concurrently
+            update_ms = (time.perf_counter() - t0) * 1e3
         eta = grp.eta()
         grp.sample_candidates(5678, total_units, 0.0, 1.0)  # ONE logical Philox sample, sharded
         eng = grp.primary
@@ -461,10 +498,12 @@ def main():
 
             def step():
                 v, i = traj.argmin()
+                last.update(winner_value=v, winner_index=i)
                 return float(v[0]), int(i[0])
         else:
             def step():
-                v, i, _ = grp.acq_argmax("ei", eta)
+                v, i, x = grp.acq_argmax("ei", eta)
+                last.update(winner_value=[v], winner_index=[i], winner_point=x)
                 return float(v), int(i)
 
         def kernel_ms_of_step():
@@ -477,13 +516,14 @@ def main():
         eng.set_hyper(1.0, ls, noise, float(Y.mean()))
         eng.set_data(X, Y)  # warm-up (allocations)
         torch.cuda.synchronize()
-        samples = []
-        for _ in range(5):  # every rank runs the same deterministic update (replicated model state); the median of five calls
-            t0 = time.perf_counter()
-            eng.set_data(X, Y)
-            torch.cuda.synchronize()
-            samples.append((time.perf_counter() - t0) * 1e3)
-        update_ms = sorted(samples)[2]
+        if args.full:
+            samples = []
+            for _ in range(5):  # every rank runs the same deterministic update (replicated model state); the median of five calls
+                t0 = time.perf_counter()
+                eng.set_data(X, Y)
+                torch.cuda.synchronize()
+                samples.append((time.perf_counter() - t0) * 1e3)
+            update_ms = sorted(samples)[2]
         eta = eng.eta()
         lo = min(rank * per, total_units)
         mine = max(0, min(lo + per, total_units) - lo)
@@ -496,6 +536,7 @@ def main():
             def step():
                 pair = eng.acq_argmax_pair("ei", eta, Xq, index_base=lo)      # enqueue only
                 v, i = all_gather_winners(eng, pair)                          # all-gather + merge + ONE sync
+                last.update(winner_value=v, winner_index=i)
                 return float(v[0]), int(i[0])
         elif kind == "qei":
             q, S = w["q"], w["S"]
@@ -508,6 +549,7 @@ def main():
                 v, i = torch.max(vals, 0)
                 pair = torch.stack([v, (i + lo).view(1).view(torch.float64)[0]])
                 gv, gi = all_gather_winners(eng, pair)
+                last.update(winner_value=gv, winner_index=gi, qei_values=vals)
                 return float(gv[0]), int(gi[0])
         else:
             F, B = w["F"], w["B"]
@@ -519,6 +561,7 @@ def main():
             def step():
                 pairs = traj.argmin_pairs(Xq, index_base=lo)
                 v, i = all_gather_winners(eng, pairs, minimize=True)
+                last.update(winner_value=v, winner_index=i)
                 return float(v[0]), int(i[0])
 
         def kernel_ms_of_step():
@@ -551,6 +594,8 @@ def main():
         per_rank_ms = [float(x) for x in all_ms.cpu()]
     elif group_mode:
         per_rank_ms = [float(m.last_kernel_ms()[0]) for m in grp.members]  # the last step's, per member
+    if args.dump_outputs and rank == 0:  # the replicated winners; qei_values: rank 0's own q-batches
+        dump_outputs(args.dump_outputs, {k: (v.cpu() if hasattr(v, "cpu") else v) for k, v in last.items()})
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -615,11 +660,13 @@ def main():
             out["roofline"].update({"bound": "mfma", "achieved": i8_achieved, "peak": I8_PEAK, "unit": "TOP/s (int8)",
                                     "frac": i8_achieved / I8_PEAK, "int8_ops_per_unit": i8_ops,
                                     "f64_equivalent_TFLOPs": achieved})
-        if nshards == 1 and not args.no_acquire and kind == "ei":
+        if update_ms is None:  # measured by --full only
+            del out["config"]["update_ms"]
+        if args.full and nshards == 1 and not args.no_acquire and kind == "ei":
             out["config"]["acquire_ms"] = end_to_end_acquire_ms(X, Y, w)
             out["config"]["fit"] = end_to_end_fit_ms(X, Y, w)
             out["config"]["small_calls_ms"] = small_call_ms(X, Y, w)
-        if (nshards == 1 and not args.no_secondary and args.workload == "headline" and args.precision == "f64"
+        if (args.full and nshards == 1 and not args.no_secondary and args.workload == "headline" and args.precision == "f64"
                 and not args.m_per_gpu and not group_mode):
             # every other workload of BASELINE.json's configs in the same driver-timed run: few steps each, same pricing
             if not group_mode:
@@ -638,7 +685,7 @@ def main():
                     sec["headline_auto"]["best"][1] == out["config"]["best_index"]
                     and abs(sec["headline_auto"]["best"][0] - out["config"]["best_value"]) <= 1e-12 * abs(out["config"]["best_value"]))
             out["secondary"] = sec
-        if not args.no_cpu_baseline and nshards == 1:
+        if args.full and not args.no_cpu_baseline and nshards == 1:
             out["cpu_baseline"] = cpu_baseline(w)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box session (via gpurun, from the repo root): the closing evidence of a round with the FINAL library.
 #   usage: tools/gpu_evidence.sh <round> [bench|traffic|update|fit|all]
-#   bench   : the driver's command (python bench.py --steps 20 --warmup 5) plain and under rocprofv3 --kernel-trace --stats
+#   bench   : the full benchmark line (python bench.py --full --steps 20 --warmup 5) plain and under rocprofv3 --kernel-trace --stats
 #   traffic : FETCH_SIZE / WRITE_SIZE passes (separate rocprofv3 --pmc runs, --kernel-trace only) of every bench line's
 #             dominant kernel -> profiles/traffic.json entries labelled with this round; wait-state counters of the AUTO sweep
 #   update  : `update` at N = 4096 / 8192: kernel trace, the persistent kernel's own time stamps, call latency
@@ -9,14 +9,14 @@
 set -u; R=${1:-r05}; WHAT=${2:-all}; OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 want() { [ "$WHAT" = all ] || [ "$WHAT" = "$1" ]; }
 if want bench; then
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err; echo "bench rc=$?"
-  ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_${R}_default_stats -o stats -- python $OLDPWD/bench.py > $OUT/${R}_bench_default_under_rocprof.json 2> $OUT/prof_${R}_default.log ); echo "default stats rc=$?"
+  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err; echo "bench rc=$?"
+  ( cd "$TMPDIR" && timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_${R}_default_stats -o stats -- python $OLDPWD/bench.py --full > $OUT/${R}_bench_default_under_rocprof.json 2> $OUT/prof_${R}_default.log ); echo "default stats rc=$?"
   python - $R <<'PY' > $OUT/${R}_rocprof_default_command.txt 2>&1
 import sqlite3, glob, sys
 R = sys.argv[1]
 p = glob.glob(f'gpurun_out/prof_{R}_default_stats/*_results.db')[0]
 cur = sqlite3.connect(p).cursor()
-print("rocprofv3 --kernel-trace --stats -- python bench.py   (the default command: headline + secondary workloads + cpu_baseline)")
+print("rocprofv3 --kernel-trace --stats -- python bench.py --full   (headline + secondary workloads + cpu_baseline)")
 print(f"{'kernel':100s} {'calls':>6s} {'total_us':>14s} {'avg_us':>14s} {'pct':>7s}")
 for name, calls, total, avg, pct in cur.execute("select * from top_kernels limit 30"):
     print(f"{name[:100]:100s} {calls:6d} {total:14.0f} {avg:14.0f} {pct:7.2f}")
