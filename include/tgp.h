@@ -74,7 +74,9 @@ enum tgp_acq {
 
 /* ---- lifetime ------------------------------------------------------------------------- */
 /* One handle == one GPR model resident on one GPU (reference: GaussianProcessRegression.__init__,
- * models/gpflow/models.py:88-134).  d = input dimension (1..32). */
+ * models/gpflow/models.py:88-134).  d = input dimension, 1..1024 (TGP_ERR_SHAPE above).  Above 32 ("wide inputs") the
+ * sweeps run in float64 only -- tgp_set_precision refuses TGP_PREC_I8X4 / TGP_PREC_I8X5 with TGP_ERR_ARG and
+ * TGP_PREC_AUTO stays on float64 -- and tgp_traj_create(_rff) refuse with TGP_ERR_SHAPE. */
 int tgp_create(int device_id, int d, int kernel_kind, tgp_handle* out);
 int tgp_destroy(tgp_handle h);
 const char* tgp_last_error(tgp_handle h); /* h may be NULL: message of the last failed create */

@@ -141,6 +141,8 @@ def load():
 
 MERGES = {"rccl": 0, "peer": 1}
 PRECISIONS = {"f64": 0, "i8x4": 1, "i8x5": 2, "auto": 3}
+MAX_D = 1024      # input dimensions tgp_create accepts (include/tgp.h)
+NARROW_MAX_D = 32  # above it: float64 sweeps only (no int8 rungs), no trajectories
 
 
 def check(lib, handle, rc, group=False):

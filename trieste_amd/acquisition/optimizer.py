@@ -27,6 +27,7 @@ from ..space import Box, DiscreteSearchSpace, SearchSpace
 NUM_SAMPLES_MIN = 5000   # optimizer.py:46-66
 NUM_SAMPLES_DIM = 1000
 NUM_RUNS_DIM = 10
+TOPK_MAX = 1024          # tgp_acq_topk's k; more starts (the default optimizer at d > 102) rank the swept values on the host
 
 
 class FailedOptimizationError(Exception):
@@ -138,8 +139,8 @@ def generate_initial_points(num_initial_points: int, initial_sampler, space: Sea
         cand = _to_host(candidates)
         if cand.ndim != 2:
             raise ValueError(f"The initial samples must be a tensor of rank 2, got a tensor of rank {cand.ndim}.")
-        if vectorization == 1 and hasattr(target_func, "top_k"):
-            k = min(num_initial_points, cand.shape[0])
+        k = min(num_initial_points, cand.shape[0])
+        if vectorization == 1 and hasattr(target_func, "top_k") and k <= TOPK_MAX:
             v, i = target_func.top_k(candidates, k)
             vals, pts = np.asarray(v)[None, :], cand[np.asarray(i)][None, :, :]
         else:

@@ -15,7 +15,8 @@ from .function import BatchMonteCarloExpectedImprovement, ExpectedImprovement
 from .interface import (AcquisitionFunctionBuilder, GreedyAcquisitionFunctionBuilder, SingleModelAcquisitionBuilder,
                         SingleModelGreedyAcquisitionBuilder, VectorizedAcquisitionFunctionBuilder)
 from .optimizer import _fresh_seed, automatic_optimizer_selector, batchify_joint, batchify_vectorize
-from .sampler import ExactThompsonSampler, ThompsonSampler
+from .._lib import NARROW_MAX_D
+from .sampler import ExactThompsonSampler, ThompsonSampler, ThompsonSamplerFromTrajectory
 from .utils import select_nth_output
 
 
@@ -142,6 +143,8 @@ class DiscreteThompsonSampling(AcquisitionRule):
             raise ValueError(f"datasets must be provided and contain the single key {OBJECTIVE}")
         model = models[OBJECTIVE]
         eng = getattr(model, "engine", None)
+        if isinstance(self._thompson_sampler, ThompsonSamplerFromTrajectory) and eng is not None and eng.d > NARROW_MAX_D:
+            raise ValueError(f"Thompson sampling from trajectories supports input dimensions up to {NARROW_MAX_D}, got {eng.d}")
         if self._on_device and eng is not None and hasattr(search_space, "sample_device") and hasattr(eng, "sample_box"):
             query_points = search_space.sample_device(eng, self._num_search_space_samples,
                                                       seed=_fresh_seed() if self._seed is None else self._seed)

@@ -177,7 +177,7 @@ int gemm_tall(tgp_handle h, bool tb, int m, int n, int k, double alpha, const do
 constexpr double AUTO_DEMOTE = 0.10;
 constexpr int64_t I8_MAX_N = 16384;  // int32 accumulators: 5 pairs x 2^14 x N < 2^31
 int auto_rung_precision(tgp_handle h) {
-  if (h->N > I8_MAX_N) return TGP_PREC_F64;
+  if (h->N > I8_MAX_N || h->dp > MAX_D) return TGP_PREC_F64;   // (no int8 sweep for wide inputs)
   if (h->auto_level == 0) return TGP_PREC_I8X4;
   if (h->auto_level == 1 && h->dp <= 16) return TGP_PREC_I8X5;
   return TGP_PREC_F64;
@@ -306,7 +306,16 @@ bool plan_split(SweepArgs& am, int nb, int g) {
   return ok;
 }
 
-hipError_t launch_sweep_kind(tgp_handle h, const SweepArgs& a, bool joint, int64_t wgrid) {
+hipError_t launch_sweep_kind(tgp_handle h, const SweepArgs& a0, bool joint, int64_t wgrid) {
+  const SweepArgs* ap = &a0;
+  SweepArgs aw;
+  if (a0.m.dp > MAX_D) {  // wide inputs: the candidate coordinates of each workgroup's block go to device scratch, not LDS
+    if (hipError_t e = h->s_xqw.reserve((size_t)wgrid * (size_t)a0.m.dp * SW_BN * sizeof(double))) return e;
+    aw = a0;
+    aw.xqw = h->s_xqw.as<double>();
+    ap = &aw;
+  }
+  const SweepArgs& a = *ap;
   switch (h->kind) {
     case TGP_RBF: return launch_sweep_kind0(h->stream, a, joint, wgrid);
     case TGP_MATERN12: return launch_sweep_kind1(h->stream, a, joint, wgrid);
@@ -973,7 +982,7 @@ const char* tgp_last_error(tgp_handle h) { return h ? h->err.c_str() : g_create_
 int tgp_create(int device_id, int d, int kernel_kind, tgp_handle* out) {
   if (!out) return fail(nullptr, TGP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (d < 1 || d > MAX_D) return fail(nullptr, TGP_ERR_SHAPE, "d must be in 1..%d, got %d", MAX_D, d);
+  if (d < 1 || d > MAX_D_WIDE) return fail(nullptr, TGP_ERR_SHAPE, "d must be in 1..%d, got %d", MAX_D_WIDE, d);
   if (kernel_kind < 0 || kernel_kind > 3)
     return fail(nullptr, TGP_ERR_ARG, "unknown kernel kind %d", kernel_kind);
   int ndev = 0;
@@ -1017,7 +1026,7 @@ int tgp_destroy(tgp_handle h) {
   }
   for (DevBuf* b : {&h->d_xn, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
                     &h->d_err, &h->d_tmp1, &h->d_tmp2, &h->d_info, &h->d_pen, &h->d_ent, &h->d_repv, &h->d_wq, &h->d_rs, &h->d_xsa, &h->s_ent, &h->s_in, &h->s_in2, &h->s_out1,
-                    &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_rep,
+                    &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_xqw, &h->s_rep,
                     &h->s_rep_stats, &h->d_dag_flags, &h->d_dag_trace})
     b->release();
 
@@ -1049,6 +1058,9 @@ int tgp_set_precision(tgp_handle h, int precision) {
     return fail(h, TGP_ERR_ARG, "unknown precision %d", precision);
   if (precision == TGP_PREC_I8X5 && h->dp > 16)
     return fail(h, TGP_ERR_ARG, "TGP_PREC_I8X5 supports input dimensions up to 16 (LDS), got %d", h->d);
+  if (precision == TGP_PREC_I8X4 && h->dp > MAX_D)
+    return fail(h, TGP_ERR_ARG, "TGP_PREC_I8X4 supports input dimensions up to %d (wide inputs sweep in float64), got %d", MAX_D,
+                h->d);
   h->precision_req = precision;
   h->precision = precision == TGP_PREC_AUTO ? TGP_PREC_F64 : precision;  // AUTO: resolved at the next plain sweep
   h->repair = false;
@@ -1285,7 +1297,7 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
     uint32_t* const tflags = h->d_tmp1.as<uint32_t>();  // [Npad / 128] words of the Npad doubles
     HIPCHK(h, hipMemsetAsync(tflags, 0, (size_t)(Npad / 128) * sizeof(uint32_t), s));
     launch_block_trsv(s, L, W, Npad, (int)(Npad / 128), h->d_err.as<double>(), h->d_alpha.as<double>(), tflags);
-    HIPCHK(h, h->s_small.reserve(64 + (MAX_D + 8) * sizeof(double)));
+    HIPCHK(h, h->s_small.reserve(64 + (std::max(h->dp, MAX_D) + 8) * sizeof(double)));
     trial_out = h->s_small.as<double>() + 8;
     launch_nlml_value(s, model_dev(h), L, h->d_alpha.as<double>(), trial_out);
   } else {
@@ -1295,7 +1307,7 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
     launch_trmv(s, A, Npad, Npad, h->d_tmp2.as<double>(), h->d_alpha.as<double>(), false);
     // the padding rows of W carry the identity: alpha/tmp there are err_pad = 0 -> stay 0.
     if (trial_value) {  // (below the persistent kernel's sizes a trial is a full update)
-      HIPCHK(h, h->s_small.reserve(64 + (MAX_D + 8) * sizeof(double)));
+      HIPCHK(h, h->s_small.reserve(64 + (std::max(h->dp, MAX_D) + 8) * sizeof(double)));
       trial_out = h->s_small.as<double>() + 8;
       launch_nlml_value(s, model_dev(h), L, h->d_err.as<double>(), trial_out);
     }
@@ -1356,6 +1368,10 @@ static BatchScratch& batch_scratch(int device) {
 }
 
 static constexpr size_t TRIAL_SMALL_PER = 40 + (MAX_D + 8);  // ls [32], variance, noise, mean (32 .. 34), value slots from 40
+// wide inputs (dp > MAX_D): variance, noise, mean stay at 32 .. 34 and the value at 40 (what assemble_K_kernel / batch_prep_kernel /
+// the value kernel read), the lengthscales move behind them, [TRIAL_WIDE_LS, TRIAL_WIDE_LS + dp)
+static size_t trial_small_per(int dp) { return dp > MAX_D ? TRIAL_WIDE_LS + (size_t)dp : TRIAL_SMALL_PER; }
+static size_t trial_ls_off(int dp) { return dp > MAX_D ? TRIAL_WIDE_LS : 0; }
 static int nlml_trial_enqueue(tgp_handle h, BatchScratch& bs, int B, double* small, int* infos, uint32_t* ctrl_copy) {
   const int64_t N = h->N, Npad = h->Npad;
   const int d = h->d, dp = h->dp, NB = (int)(Npad / 128);
@@ -1368,7 +1384,7 @@ static int nlml_trial_enqueue(tgp_handle h, BatchScratch& bs, int B, double* sma
   h->dag_last_slot = slot;
   const size_t nflags = (size_t)plan.ntasks + 2 * (size_t)NB;
   const size_t state_words = (size_t)B * nflags + DAG_CTRL_WORDS + (size_t)B * plan.ntasks;
-  const size_t small_per = TRIAL_SMALL_PER;
+  const size_t small_per = trial_small_per(dp);
   // [B] scaled inputs Xs [Npad][dp]; [B] centred targets err [Npad]; [B] z [Npad]; the trsv flags [B][NB]
   const size_t xs_per = (size_t)Npad * dp;
   double* const mats = bs.mats.as<double>();
@@ -1476,7 +1492,7 @@ int tgp_nlml_trial_batch(tgp_handle h, const double* hypers, int B, double* valu
   const int64_t Np = h->Npad;
   const int dp = h->dp, NB = (int)(Np / 128);
   const size_t nn = (size_t)Np * Np, per = 3 * nn * sizeof(double);
-  const size_t small_per = TRIAL_SMALL_PER;
+  const size_t small_per = trial_small_per(dp);
   BatchScratch& bs = batch_scratch(h->device);
   std::unique_lock<std::mutex> scratch_lock(bs.mu);
   // whatever leaves this function early from here on first waits for what it has enqueued: the scratch is shared
@@ -1549,7 +1565,7 @@ int tgp_nlml_trial_batch(tgp_handle h, const double* hypers, int B, double* valu
   std::vector<double> hsmall(small_doubles, 0.0);  // (also zeroes the breakdown reports and the error words)
   for (int b = 0; b < B; ++b) {
     const double* hb = hypers + (size_t)b * (d + 3);
-    for (int c = 0; c < dp; ++c) hsmall[(size_t)b * small_per + c] = c < d ? hb[1 + c] : 1.0;
+    for (int c = 0; c < dp; ++c) hsmall[(size_t)b * small_per + trial_ls_off(dp) + c] = c < d ? hb[1 + c] : 1.0;
     hsmall[(size_t)b * small_per + 32] = hb[0];      // variance
     hsmall[(size_t)b * small_per + 33] = hb[1 + d];  // noise variance
     hsmall[(size_t)b * small_per + 34] = hb[2 + d];  // constant mean
@@ -1784,10 +1800,10 @@ int tgp_nlml(tgp_handle h, double* value, double* grad) {
   if (int rc = set_device(h)) return rc;
   const int64_t Npad = h->Npad;
   const int np = h->d + 4;
-  HIPCHK(h, h->s_small.reserve(64 + (MAX_D + 8) * sizeof(double)));
+  HIPCHK(h, h->s_small.reserve(64 + (std::max(h->dp, MAX_D) + 8) * sizeof(double)));
   double* out = h->s_small.as<double>() + 8;
   if (grad) {
-    HIPCHK(h, h->s_blkv.reserve((size_t)nlml_blocks(Npad) * (MAX_D + 2) * sizeof(double)));
+    HIPCHK(h, h->s_blkv.reserve((size_t)nlml_blocks(Npad) * (std::max(h->dp, MAX_D) + 2) * sizeof(double)));
     HIPCHK(h, h->s_grad.reserve((size_t)Npad * Npad * sizeof(double)));
     double* Kinv = h->s_grad.as<double>();
     // Kinv = W^T W  (Wt is in d_A, W in d_W; both carry explicit zeros outside their triangles)
@@ -1976,7 +1992,7 @@ int tgp_acq_value_grad(tgp_handle h, int acq_kind, double param, const double* X
   if (int rc = stage_out_prepare(h, h->s_out1, val, P, where, &dval)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)P * h->d, where, &dgrad)) return rc;
   const int64_t Nscratch = (acq_kind == TGP_ACQ_GIBBON && h->rep_twin) ? std::max(Npad, h->rep_twin->Npad) : Npad;
-  HIPCHK(h, h->s_grad.reserve(((size_t)3 * Nscratch * Ppad + grad_tail_scratch_doubles(Ppad)) * sizeof(double)));
+  HIPCHK(h, h->s_grad.reserve(((size_t)3 * Nscratch * Ppad + grad_tail_scratch_doubles(Ppad, h->dp)) * sizeof(double)));
   double* B = h->s_grad.as<double>();
   double* C1 = B + (size_t)Npad * Ppad;
   double* Z = C1 + (size_t)Npad * Ppad;
@@ -2092,7 +2108,7 @@ int tgp_joint_vjp(tgp_handle h, const double* Xq, int64_t G, int q, const double
   if (int rc = stage_in(h, h->s_in2, gmean, (size_t)P, where, &dgm)) return rc;
   if (int rc = stage_in(h, h->s_out2, gcov, (size_t)P * q, where, &dgc)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, grad, (size_t)P * h->d, where, &dgrad)) return rc;
-  HIPCHK(h, h->s_grad.reserve(((size_t)4 * Npad * Ppad + grad_tail_scratch_doubles(Ppad)) * sizeof(double)));
+  HIPCHK(h, h->s_grad.reserve(((size_t)4 * Npad * Ppad + grad_tail_scratch_doubles(Ppad, h->dp)) * sizeof(double)));
   double* B = h->s_grad.as<double>();
   double* C1 = B + (size_t)Npad * Ppad;
   double* D = C1 + (size_t)Npad * Ppad;
@@ -2133,7 +2149,7 @@ int tgp_qei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, const d
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)P * h->d, where, &dgrad)) return rc;
-  const size_t part_doubles = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad));
+  const size_t part_doubles = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, h->dp));
   HIPCHK(h, h->s_grad.reserve(((size_t)4 * Npad * Ppad + (size_t)Ppad * Ppad + part_doubles + (size_t)2 * P * (1 + q)) * sizeof(double)));
   double* B = h->s_grad.as<double>();
   double* C1 = B + (size_t)Npad * Ppad;
@@ -2404,9 +2420,10 @@ int tgp_sample_box(tgp_handle h, uint64_t seed, int64_t first, int64_t M, const 
   if (M < 0 || !lower || !upper || (M > 0 && !out_device)) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (M == 0) return TGP_OK;
   if (int rc = set_device(h)) return rc;
-  HIPCHK(h, h->s_small.reserve(2 * MAX_D * sizeof(double) + 64));
+  const int dmax = std::max(h->dp, MAX_D);
+  HIPCHK(h, h->s_small.reserve(2 * dmax * sizeof(double) + 64));
   double* dl = h->s_small.as<double>() + 8;
-  double* du = dl + MAX_D;
+  double* du = dl + dmax;
   HIPCHK(h, hipMemcpyAsync(dl, lower, h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(du, upper, h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   launch_sample_box(h->stream, seed, first, M, h->d, dl, du, out_device);
@@ -2566,6 +2583,8 @@ int tgp_traj_create(tgp_handle h, const double* rff_W, const double* rff_b, int 
   *out = nullptr;
   if (!h->have_data) return fail(h, TGP_ERR_STATE, "model has no data: call tgp_set_data first");
   if (F < 1 || B < 1 || !rff_W || !rff_b || !w || !xi) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (h->dp > MAX_D)
+    return fail(h, TGP_ERR_SHAPE, "trajectories support input dimensions up to %d, got %d", MAX_D, h->d);
   if (int rc = set_device(h)) return rc;
   tgp_traj t = new (std::nothrow) tgp_traj_s();
   if (!t) return fail(h, TGP_ERR_ALLOC, "host allocation failed");
@@ -2641,6 +2660,8 @@ int tgp_traj_create_rff(tgp_handle h, const double* rff_W, const double* rff_b, 
   *out = nullptr;
   if (!h->have_data) return fail(h, TGP_ERR_STATE, "model has no data: call tgp_set_data first");
   if (F < 1 || B < 1 || !rff_W || !rff_b || !eps) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (h->dp > MAX_D)
+    return fail(h, TGP_ERR_SHAPE, "trajectories support input dimensions up to %d, got %d", MAX_D, h->d);
   if (int rc = set_device(h)) return rc;
   tgp_traj t = new (std::nothrow) tgp_traj_s();
   if (!t) return fail(h, TGP_ERR_ALLOC, "host allocation failed");

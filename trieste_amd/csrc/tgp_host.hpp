@@ -129,7 +129,8 @@ struct tgp_handle_s {
   int rep_m = 0;
   DevBuf d_repv;                   // [N + m][m]: the twin's last m rows of W as weight columns
   // scratch
-  DevBuf s_ent, s_in, s_in2, s_out1, s_out2, s_out3, s_blkv, s_blki, s_small, s_kcache, s_aslab, s_grad, s_ks, s_part;
+  DevBuf s_ent, s_in, s_in2, s_out1, s_out2, s_out3, s_blkv, s_blki, s_small, s_kcache, s_aslab, s_grad, s_ks, s_part,
+      s_xqw;  // wide sweeps: the per-workgroup candidate tiles (SweepArgs::xqw)
   // `update` as one persistent launch: the task list of the current block count (tgp_kernels_dag.hip)
   // one cached plan per use: 0 the full update, 1 the factor-only trial (tgp_nlml_trial), 2 .. 9 the batched
   // factor-only launch (tgp_nlml_trial_batch) per member count -- a fit alternates between them (90 draws are eleven

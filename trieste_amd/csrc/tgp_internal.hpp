@@ -10,7 +10,11 @@ namespace tgp {
 constexpr int SW_BN = 128;  // candidates per workgroup (sweep kernel)
 constexpr int NPAD_MULT = 256;  // row block of W per workgroup tile of the sweep
 constexpr int LEAF = 64;    // Cholesky / inverse leaf block
-constexpr int MAX_D = 32;
+constexpr int MAX_D = 32;        // widest padded dimension of the register-resident (DP-templated) kernels
+constexpr int WIDE_CHUNK = 32;   // d > MAX_D ("wide inputs"): dp is a multiple of this chunk width
+constexpr int MAX_D_WIDE = 1024; // the input dimension tgp_create accepts (include/tgp.h)
+constexpr int DP_WIDE = 0;       // template argument of the wide instantiations: dp is a run-time value (ModelDev::dp)
+constexpr int TRIAL_WIDE_LS = 48;  // batched trials at dp > MAX_D: a member's lengthscales sit at [48, 48 + dp) of its hyper block
 constexpr int MAX_Q = 64;
 
 inline int dpad_of(int d) {
@@ -19,7 +23,8 @@ inline int dpad_of(int d) {
   if (d <= 6) return 6;
   if (d <= 8) return 8;
   if (d <= 16) return 16;
-  return 32;
+  if (d <= 32) return 32;
+  return (d + WIDE_CHUNK - 1) / WIDE_CHUNK * WIDE_CHUNK;
 }
 
 struct ModelDev {       // device-resident model state (all pointers device)
@@ -78,6 +83,8 @@ struct SweepArgs {
   double* adv_rec;
   const int64_t* M_dev;   // SPLIT instantiation + combine kernel: the candidate count lives on the device (the
                           // repair pass over the flagged candidates is enqueued without a host round trip)
+  double* xqw;            // wide sweeps (dp > MAX_D): [grid][dp][128] per-workgroup scaled candidate coordinates (device
+                          // scratch beside the K* slabs; the narrow instantiations keep them in LDS)
 };
 constexpr double I8_TIGHT = 1.0078125;  // digit-plane scales S_i = I8_TIGHT max_k |W_ik|, S' = I8_TIGHT variance: the
                                         // balanced digits reach |q| <= 0x7f7f7f7f = 0.99609 2^31 > 2^31 / I8_TIGHT
@@ -158,7 +165,7 @@ void launch_joint_pick(hipStream_t s, const ModelDev& m, const double* Xq, int64
 void launch_joint_mix(hipStream_t s, const double* C1, const double* gcov, int64_t P, int64_t Ppad, int64_t Npad, int q, double* D);
 void launch_joint_vjp_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, int q, const double* B,
                            const double* C1, const double* Z, double* part, const double* gmean, const double* gcov, double* grad);
-size_t grad_tail_scratch_doubles(int64_t Ppad);   // `part` of launch_grad_tail
+size_t grad_tail_scratch_doubles(int64_t Ppad, int dp);   // `part` of launch_grad_tail / launch_joint_vjp_tail
 void launch_grad_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad,
                       const double* B, const double* C1, const double* Z, double* part, int acq, double param, double* val,
                       double* grad, const double* samples = nullptr, int S = 0, double rep_w = 0.0,

@@ -148,7 +148,13 @@ void launch_theta_tail(hipStream_t s, const double* mean, int64_t ldm, const dou
 }
 
 constexpr int GT_THREADS = 256, GT_KS = 16, GT_J = 2 + 2 * MAX_D;
-size_t grad_tail_scratch_doubles(int64_t Ppad) { return (size_t)GT_KS * (size_t)Ppad * GT_J; }
+// the partial layout part[ks][p][j]: j = 0 mean, 1 sum c^2, 2 + c d mean / dx_c, GV + c the d var sum.  Up to dp = MAX_D a point
+// holds GT_J sums with GV = 2 + MAX_D; wide inputs hold 2 + 2 dp with GV = 2 + dp, followed by the scaled query points [Ppad][dp]
+__host__ __device__ static int gt_j(int dp) { return dp > MAX_D ? 2 + 2 * dp : GT_J; }
+__host__ __device__ static int gt_v(int dp) { return dp > MAX_D ? 2 + dp : 2 + MAX_D; }
+size_t grad_tail_scratch_doubles(int64_t Ppad, int dp) {
+  return (size_t)GT_KS * (size_t)Ppad * gt_j(dp) + (dp > MAX_D ? (size_t)Ppad * dp : 0);
+}
 
 // Value and gradient of the acquisition function at P points from B = K*^T [N][Ppad], C1 = W K*, Z = K^-1 k* (same layout):
 //   mean = sum_k B alpha,  var = s_f^2 - sum_k C1^2,  d mean / dx = sum_k alpha dk/dx,  d var / dx = -2 sum_k Z dk/dx.
@@ -237,18 +243,108 @@ __global__ __launch_bounds__(GT_THREADS) void grad_partial_kernel(ModelDev m, co
   }
 }
 
+// Wide inputs (dp > MAX_D): grid (Ppad / 16, GT_KS, dp / WIDE_CHUNK) -- the workgroup of chunk z computes r^2 over all dp
+// coordinates (of the query points scaled beforehand, xsq [Ppad][dp]) and keeps only its own chunk's gradient sums, so the per-lane
+// arrays and the LDS reduction are those of dp = WIDE_CHUNK; chunk 0 also carries the mean and sum c^2.
+__global__ __launch_bounds__(GT_THREADS) void grad_partial_wide_kernel(ModelDev m, const double* __restrict__ xsq, int64_t P,
+                                                                       int64_t Ppad, const double* __restrict__ B,
+                                                                       const double* __restrict__ C1,
+                                                                       const double* __restrict__ Z,
+                                                                       double* __restrict__ part) {
+  constexpr int WC = WIDE_CHUNK;
+  static_assert(2 + 2 * WC <= GT_J, "a chunk's sums fit the reduction buffer of the narrow kernel");
+  __shared__ double red[4][16][2 + 2 * WC + 1];
+  const int d = m.d, dp = m.dp, tid = threadIdx.x, pl = tid & 15, kl = tid >> 4, w = tid >> 6, lane = tid & 63;
+  const int64_t p = 16 * (int64_t)blockIdx.x + pl, pc = p < P ? p : P - 1;
+  const int ks = blockIdx.y, c0 = blockIdx.z * WC, gj = gt_j(dp), gv0 = gt_v(dp);
+  const int64_t chunk = (m.Npad + GT_KS - 1) / GT_KS;
+  const int64_t k0 = ks * chunk, k1 = (k0 + chunk < m.N) ? k0 + chunk : m.N;
+  const double* const xq = xsq + pc * dp;
+  double xs[WC], ls[WC];
+#pragma unroll
+  for (int c = 0; c < WC; ++c) {
+    ls[c] = m.ls[c0 + c];
+    xs[c] = xq[c0 + c];
+  }
+  double mean = 0.0, ssq = 0.0;
+  double gm[WC], gv[WC];
+#pragma unroll
+  for (int c = 0; c < WC; ++c) gm[c] = gv[c] = 0.0;
+  for (int64_t k = k0 + kl; k < k1; k += 16) {
+    const double kv = B[k * Ppad + p], ck = C1[k * Ppad + p], zk = Z[k * Ppad + p];
+    const double al = m.alpha[k];
+    mean = fma(kv, al, mean);
+    ssq = fma(ck, ck, ssq);
+    const double* const xk = m.Xs + k * dp;
+    double r2 = 0.0;
+    for (int cc = 0; cc < dp; cc += 8) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const double t = xq[cc + u] - xk[cc + u];
+        r2 = fma(t, t, r2);
+      }
+    }
+    const double f1 = 2.0 * kernel_dr2(m.kind, r2, m.variance);
+#pragma unroll
+    for (int c = 0; c < WC; ++c) {
+      const double dk = f1 * (xs[c] - xk[c0 + c]) / ls[c];
+      gm[c] = fma(al, dk, gm[c]);
+      gv[c] = fma(zk, dk, gv[c]);
+    }
+  }
+  auto fold = [&](double v) {
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    return v;
+  };
+  mean = fold(mean);
+  ssq = fold(ssq);
+#pragma unroll
+  for (int c = 0; c < WC; ++c) {
+    gm[c] = fold(gm[c]);
+    gv[c] = fold(gv[c]);
+  }
+  if (lane < 16) {
+    red[w][pl][0] = mean;
+    red[w][pl][1] = ssq;
+#pragma unroll
+    for (int c = 0; c < WC; ++c) {
+      red[w][pl][2 + c] = gm[c];
+      red[w][pl][2 + WC + c] = gv[c];
+    }
+  }
+  __syncthreads();
+  if (tid < 16) {
+    double* const out = part + ((size_t)ks * Ppad + p) * gj;
+    auto tot = [&](int j) { return (red[0][pl][j] + red[1][pl][j]) + (red[2][pl][j] + red[3][pl][j]); };
+    if (blockIdx.z == 0) {
+      out[0] = tot(0);
+      out[1] = tot(1);
+    }
+    for (int c = 0; c < WC && c0 + c < d; ++c) {
+      out[2 + c0 + c] = tot(2 + c);
+      out[gv0 + c0 + c] = tot(2 + WC + c);
+    }
+  }
+}
+
 // one workgroup per point: thread j adds the GT_KS partials of sum j in order (coalesced over j), thread 0 evaluates the tail
+// (WIDE: the wide partial layout; thread 0 sums the two value terms' partials and leaves the tail's derivatives in LDS, then the
+// threads take the coordinates in turn)
+template <bool WIDE>
 __global__ __launch_bounds__(128) void grad_finish_kernel(ModelDev m, int64_t P, int64_t Ppad,
                                                           const double* __restrict__ part, int acq, double param,
                                                           const double* __restrict__ samples, int S, double rep_w,
                                                           double accum, double* __restrict__ val,
                                                           double* __restrict__ grad) {
   __shared__ double sums[GT_J];
+  __shared__ double coef[3];
   const int64_t p = blockIdx.x;
   const int d = m.d, j = threadIdx.x;
-  if (j < GT_J) {
+  const int gj = WIDE ? gt_j(m.dp) : GT_J;
+  if (j < (WIDE ? 2 : GT_J)) {
     double s = 0.0;
-    for (int ks = 0; ks < GT_KS; ++ks) s += part[((size_t)ks * Ppad + p) * GT_J + j];
+    for (int ks = 0; ks < GT_KS; ++ks) s += part[((size_t)ks * Ppad + p) * gj + j];
     sums[j] = s;
   }
   __syncthreads();
@@ -292,9 +388,31 @@ __global__ __launch_bounds__(128) void grad_finish_kernel(ModelDev m, int64_t P,
     }
     // accum != 0: add accum * (value, gradient) to what is there (the conditioned twin's half of the repulsion)
     val[p] = accum != 0.0 ? val[p] + accum * v : v;
-    for (int c = 0; c < d; ++c) {
-      const double dmu = tot(2 + c);
-      const double dvar = clipped ? 0.0 : -2.0 * tot(2 + MAX_D + c);  // clip_by_value has zero gradient
+    if constexpr (WIDE) {
+      coef[0] = dv_dmu;
+      coef[1] = dv_dvar;
+      coef[2] = clipped ? 1.0 : 0.0;
+    } else {
+      for (int c = 0; c < d; ++c) {
+        const double dmu = tot(2 + c);
+        const double dvar = clipped ? 0.0 : -2.0 * tot(2 + MAX_D + c);  // clip_by_value has zero gradient
+        const double g = dv_dmu * dmu + dv_dvar * dvar;
+        grad[p * d + c] = accum != 0.0 ? grad[p * d + c] + accum * g : g;
+      }
+    }
+  }
+  if constexpr (WIDE) {
+    __syncthreads();
+    const int gv0 = gt_v(m.dp);
+    const double dv_dmu = coef[0], dv_dvar = coef[1];
+    const bool clipped = coef[2] != 0.0;
+    for (int c = j; c < d; c += blockDim.x) {
+      double dmu = 0.0, sv = 0.0;
+      for (int ks = 0; ks < GT_KS; ++ks) {
+        dmu += part[((size_t)ks * Ppad + p) * gj + 2 + c];
+        sv += part[((size_t)ks * Ppad + p) * gj + gv0 + c];
+      }
+      const double dvar = clipped ? 0.0 : -2.0 * sv;  // clip_by_value has zero gradient
       const double g = dv_dmu * dmu + dv_dvar * dvar;
       grad[p * d + c] = accum != 0.0 ? grad[p * d + c] + accum * g : g;
     }
@@ -392,17 +510,17 @@ __global__ void joint_mix_kernel(const double* __restrict__ C1, const double* __
   D[k * Ppad + p] = v;
 }
 
-__global__ __launch_bounds__(64) void joint_vjp_finish_kernel(ModelDev m, const double* __restrict__ Xq, int64_t P,
-                                                              int64_t Ppad, int q, const double* __restrict__ part,
-                                                              const double* __restrict__ gmean,
-                                                              const double* __restrict__ gcov, double* __restrict__ grad) {
+// coordinate c of point p = blockIdx.x: the GT_KS partials in order (layout gj / gv0, see gt_j) and the group's cross terms
+__device__ __forceinline__ void joint_vjp_coord(const ModelDev& m, const double* __restrict__ Xq, int64_t Ppad, int q,
+                                                const double* __restrict__ part, int gj, int gv0,
+                                                const double* __restrict__ gmean, const double* __restrict__ gcov,
+                                                double* __restrict__ grad, int c) {
   const int64_t p = blockIdx.x;
-  const int d = m.d, c = threadIdx.x;
-  if (c >= d) return;
+  const int d = m.d;
   double sa = 0.0, sz = 0.0;
   for (int ks = 0; ks < GT_KS; ++ks) {
-    sa += part[((size_t)ks * Ppad + p) * GT_J + 2 + c];
-    sz += part[((size_t)ks * Ppad + p) * GT_J + 2 + MAX_D + c];
+    sa += part[((size_t)ks * Ppad + p) * gj + 2 + c];
+    sz += part[((size_t)ks * Ppad + p) * gj + gv0 + c];
   }
   double g = gmean[p] * sa - sz;
   const int64_t grp = p / q, i = p - grp * q;
@@ -420,6 +538,20 @@ __global__ __launch_bounds__(64) void joint_vjp_finish_kernel(ModelDev m, const 
     g = fma(G[i * q + j] + G[j * q + i], f1 * tc / m.ls[c], g);
   }
   grad[p * d + c] = g;
+}
+
+// (WIDE: the wide partial layout, the 64 threads take the coordinates in turn)
+template <bool WIDE>
+__global__ __launch_bounds__(64) void joint_vjp_finish_kernel(ModelDev m, const double* __restrict__ Xq, int64_t P,
+                                                              int64_t Ppad, int q, const double* __restrict__ part,
+                                                              const double* __restrict__ gmean,
+                                                              const double* __restrict__ gcov, double* __restrict__ grad) {
+  if constexpr (WIDE) {
+    for (int c = threadIdx.x; c < m.d; c += 64) joint_vjp_coord(m, Xq, Ppad, q, part, gt_j(m.dp), gt_v(m.dp), gmean, gcov, grad, c);
+  } else {
+    if ((int)threadIdx.x >= m.d) return;
+    joint_vjp_coord(m, Xq, Ppad, q, part, GT_J, 2 + MAX_D, gmean, gcov, grad, (int)threadIdx.x);
+  }
 }
 
 // cov[g][i][j] = k(x_i, x_j) - S[g q + i][g q + j], the diagonal clipped at the floor (reference interface.py:126-133); S = C1^T C1
@@ -463,12 +595,22 @@ void launch_joint_vjp_tail(hipStream_t s, const ModelDev& m, const double* Xq, i
                            const double* C1, const double* Z, double* part, const double* gmean, const double* gcov,
                            double* grad) {
   launch_grad_partial(s, m, Xq, P, Ppad, B, C1, Z, part);
-  hipLaunchKernelGGL(joint_vjp_finish_kernel, dim3((unsigned)P), dim3(64), 0, s, m, Xq, P, Ppad, q, part, gmean, gcov, grad);
+  if (m.dp > MAX_D)
+    hipLaunchKernelGGL(joint_vjp_finish_kernel<true>, dim3((unsigned)P), dim3(64), 0, s, m, Xq, P, Ppad, q, part, gmean, gcov, grad);
+  else
+    hipLaunchKernelGGL(joint_vjp_finish_kernel<false>, dim3((unsigned)P), dim3(64), 0, s, m, Xq, P, Ppad, q, part, gmean, gcov, grad);
 }
 
 static void launch_grad_partial(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, const double* B,
                                 const double* C1, const double* Z, double* part) {
   const dim3 grid((unsigned)(Ppad / 16), (unsigned)GT_KS);
+  if (m.dp > MAX_D) {   // the query points scaled once, behind the wide partials (grad_tail_scratch_doubles)
+    double* const xsq = part + (size_t)GT_KS * (size_t)Ppad * gt_j(m.dp);
+    launch_scale_inputs(s, Xq, m.ls, xsq, P, Ppad, m.d, m.dp);
+    hipLaunchKernelGGL(grad_partial_wide_kernel, dim3((unsigned)(Ppad / 16), (unsigned)GT_KS, (unsigned)(m.dp / WIDE_CHUNK)),
+                       dim3(GT_THREADS), 0, s, m, xsq, P, Ppad, B, C1, Z, part);
+    return;
+  }
   if (m.dp == 2) hipLaunchKernelGGL(grad_partial_kernel<2>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
   else if (m.dp == 4) hipLaunchKernelGGL(grad_partial_kernel<4>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
   else if (m.dp == 6) hipLaunchKernelGGL(grad_partial_kernel<6>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
@@ -481,8 +623,12 @@ void launch_grad_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_
                       const double* B, const double* C1, const double* Z, double* part, int acq, double param, double* val,
                       double* grad, const double* samples, int S, double rep_w, double accum) {
   launch_grad_partial(s, m, Xq, P, Ppad, B, C1, Z, part);
-  hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)P), dim3(128), 0, s, m, P, Ppad, part, acq, param,
-                     samples, S, rep_w, accum, val, grad);
+  if (m.dp > MAX_D)
+    hipLaunchKernelGGL(grad_finish_kernel<true>, dim3((unsigned)P), dim3(128), 0, s, m, P, Ppad, part, acq, param, samples, S, rep_w,
+                       accum, val, grad);
+  else
+    hipLaunchKernelGGL(grad_finish_kernel<false>, dim3((unsigned)P), dim3(128), 0, s, m, P, Ppad, part, acq, param, samples, S,
+                       rep_w, accum, val, grad);
 }
 
 }  // namespace tgp
@@ -561,6 +707,127 @@ __global__ __launch_bounds__(256) void nlml_grad_kernel(ModelDev m, const double
   }
 }
 
+// Wide inputs (dp > MAX_D): grid (Npad / 64, Npad / 64, dp / WIDE_CHUNK) -- the workgroup of chunk z computes r^2 over all dp
+// coordinates and accumulates only its own chunk's lengthscale terms (chunk 0 also the variance and noise terms); `partial` keeps
+// the [term][block] layout of d + 2 rows.
+__global__ __launch_bounds__(256) void nlml_grad_wide_kernel(ModelDev m, const double* __restrict__ Kinv,
+                                                             double* __restrict__ partial) {
+  constexpr int WC = WIDE_CHUNK;
+  __shared__ double red[4][WC + 2];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int d = m.d, dp = m.dp, c0 = blockIdx.z * WC;
+  const int64_t nblk = (int64_t)gridDim.x * gridDim.y, b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+  // this workgroup's terms: the lengthscales c0 .. c0 + WC (those < d), and for chunk 0 the variance and noise (rows d, d + 1)
+  auto row_of = [&](int t) { return t < WC ? c0 + t : d + (t - WC); };
+  auto live = [&](int t) { return t < WC ? c0 + t < d : blockIdx.z == 0; };
+  if (blockIdx.x > blockIdx.y) {
+    if (tid < WC + 2 && live(tid)) partial[(int64_t)row_of(tid) * nblk + b] = 0.0;
+    return;
+  }
+  const double sym = (blockIdx.x == blockIdx.y) ? 1.0 : 2.0;
+  const int64_t j = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t i0 = (int64_t)blockIdx.y * 64 + w * 16;
+  const bool jv = j < m.N;
+  double acc[WC + 2], xj[WC];
+#pragma unroll
+  for (int c = 0; c < WC + 2; ++c) acc[c] = 0.0;
+#pragma unroll
+  for (int c = 0; c < WC; ++c) xj[c] = m.Xs[j * dp + c0 + c];
+  const double aj = m.alpha[j];
+  const double* const xjr = m.Xs + j * dp;
+  for (int r = 0; r < 16; ++r) {
+    const int64_t i = i0 + r;
+    if (i >= m.N) break;  // wave-uniform
+    const double G = jv ? Kinv[i * m.Npad + j] - m.alpha[i] * aj : 0.0;
+    const double* const xi = m.Xs + i * dp;
+    double r2 = 0.0;
+    for (int cc = 0; cc < dp; cc += 8) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const double t = xi[cc + u] - xjr[cc + u];
+        r2 += t * t;
+      }
+    }
+    const double f1 = G * kernel_dr2(m.kind, r2, m.variance);
+#pragma unroll
+    for (int c = 0; c < WC; ++c) {
+      const double t = xi[c0 + c] - xj[c];
+      acc[c] = fma(f1, t * t, acc[c]);
+    }
+    acc[WC] = fma(G, kernel_rt(m.kind, r2, m.variance), acc[WC]);
+    acc[WC + 1] += (i == j) ? G : 0.0;
+  }
+#pragma unroll
+  for (int c = 0; c < WC + 2; ++c) {
+    const double s = wave_sum(acc[c]);
+    if (lane == 0) red[w][c] = s;
+  }
+  __syncthreads();
+  if (tid < WC + 2 && live(tid)) {
+    const int row = row_of(tid);
+    double v = sym * ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]));
+    if (row < d) v *= -2.0 / m.ls[row];
+    else if (row == d) v /= m.variance;
+    partial[(int64_t)row * nblk + b] = v;
+  }
+}
+
+// The final reduction for wide inputs: the same sums as nlml_final_kernel (value terms in the same order), the d + 2 gradient
+// rows a chunk of WIDE_CHUNK at a time; value only (partial == nullptr): out[0] alone.
+__global__ __launch_bounds__(1024) void nlml_final_wide_kernel(ModelDev m, const double* __restrict__ L,
+                                                               const double* __restrict__ err,
+                                                               const double* __restrict__ partial, int64_t nblocks,
+                                                               double* __restrict__ out, int64_t l_stride = 0,
+                                                               int64_t v_stride = 0, int64_t o_stride = 0) {
+  constexpr int WC = WIDE_CHUNK;
+  L += (int64_t)blockIdx.x * l_stride;
+  err += (int64_t)blockIdx.x * v_stride;
+  m.alpha += (int64_t)blockIdx.x * v_stride;
+  out += (int64_t)blockIdx.x * o_stride;
+  __shared__ double red[16][WC];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = (int)(blockDim.x >> 6);
+  const int np = m.d + 2;
+  auto tot = [&](int c) {
+    double t = 0.0;
+    for (int g = 0; g < nw; ++g) t += red[g][c];
+    return t;
+  };
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = tid; i < m.N; i += blockDim.x) {
+    acc[0] += err[i] * m.alpha[i];
+    acc[1] += log(L[i * m.Npad + i]);
+    acc[2] += m.alpha[i];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double s = wave_sum(acc[c]);
+    if (lane == 0) red[w][c] = s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    out[0] = 0.5 * tot(0) + tot(1) + 0.5 * (double)m.N * 1.8378770664093453;  // log(2 pi)
+    if (partial) out[1 + np] = -tot(2);
+  }
+  if (!partial) return;
+  for (int c0 = 0; c0 < np; c0 += WC) {
+    __syncthreads();
+    double a[WC];
+#pragma unroll
+    for (int c = 0; c < WC; ++c) {
+      a[c] = 0.0;
+      if (c0 + c < np)
+        for (int64_t b = tid; b < nblocks; b += blockDim.x) a[c] += partial[(int64_t)(c0 + c) * nblocks + b];
+    }
+#pragma unroll
+    for (int c = 0; c < WC; ++c) {
+      const double s = wave_sum(a[c]);
+      if (lane == 0) red[w][c] = s;
+    }
+    __syncthreads();
+    if (tid < WC && c0 + tid < np) out[1 + c0 + tid] = 0.5 * tot(tid);
+  }
+}
+
 // out[0] = nlml, out[1..d] = d/d lengthscale, out[d+1] = d/d variance, out[d+2] = d/d noise,
 // out[d+3] = d/d mean.  One workgroup; fixed summation order.
 // Batched value-only form (tgp_nlml_trial_batch): member blockIdx.x has its factor at L + x l_stride, its z (passed as
@@ -608,6 +875,11 @@ __global__ __launch_bounds__(1024) void nlml_final_kernel(ModelDev m, const doub
 
 // value only (find_best_model_initialization compares losses, no gradient): no K^-1, no pair reduction
 void launch_nlml_value(hipStream_t s, const ModelDev& m, const double* L, const double* err, double* out) {
+  if (m.dp > MAX_D) {
+    hipLaunchKernelGGL(nlml_final_wide_kernel, dim3(1), dim3(m.N > 1024 ? 1024 : 256), 0, s, m, L, err, (const double*)nullptr,
+                       (int64_t)0, out, (int64_t)0, (int64_t)0, (int64_t)0);
+    return;
+  }
   hipLaunchKernelGGL(nlml_final_kernel, dim3(1), dim3(m.N > 1024 ? 1024 : 256), 0, s, m, L, err, (const double*)nullptr, (int64_t)0, out);
 }
 
@@ -616,6 +888,11 @@ void launch_nlml_value_batch(hipStream_t s, const ModelDev& m, const double* L, 
                              int64_t l_stride, int64_t v_stride, int64_t o_stride) {
   ModelDev mm = m;
   mm.alpha = z;
+  if (m.dp > MAX_D) {
+    hipLaunchKernelGGL(nlml_final_wide_kernel, dim3((unsigned)B), dim3(m.N > 1024 ? 1024 : 256), 0, s, mm, L, z,
+                       (const double*)nullptr, (int64_t)0, out, l_stride, v_stride, o_stride);
+    return;
+  }
   hipLaunchKernelGGL(nlml_final_kernel, dim3((unsigned)B), dim3(m.N > 1024 ? 1024 : 256), 0, s, mm, L, z, (const double*)nullptr,
                      (int64_t)0, out, l_stride, v_stride, o_stride);
 }
@@ -625,6 +902,13 @@ int64_t nlml_blocks(int64_t Npad) { return (Npad / 64) * (Npad / 64); }
 void launch_nlml(hipStream_t s, const ModelDev& m, const double* Kinv, const double* L, const double* err,
                  double* partial, double* out) {
   dim3 grid((unsigned)(m.Npad / 64), (unsigned)(m.Npad / 64));
+  if (m.dp > MAX_D) {
+    hipLaunchKernelGGL(nlml_grad_wide_kernel, dim3(grid.x, grid.y, (unsigned)(m.dp / WIDE_CHUNK)), dim3(256), 0, s, m, Kinv,
+                       partial);
+    hipLaunchKernelGGL(nlml_final_wide_kernel, dim3(1), dim3(m.N > 1024 ? 1024 : 256), 0, s, m, L, err, partial,
+                       nlml_blocks(m.Npad), out, (int64_t)0, (int64_t)0, (int64_t)0);
+    return;
+  }
   switch (m.dp) {
     case 2: hipLaunchKernelGGL(nlml_grad_kernel<2>, grid, dim3(256), 0, s, m, Kinv, partial); break;
     case 4: hipLaunchKernelGGL(nlml_grad_kernel<4>, grid, dim3(256), 0, s, m, Kinv, partial); break;

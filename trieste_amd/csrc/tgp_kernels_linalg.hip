@@ -29,8 +29,9 @@ void launch_scale_inputs(hipStream_t s, const double* X, const double* ls, doubl
 }
 
 // Batched trial evaluations (tgp_nlml_trial_batch): member b = blockIdx.y has its own lengthscales / mean (hyp + b
-// hyp_stride: ls [dp] at 0, variance at 32, noise at 33, mean at 34) -- its scaled inputs and centred targets in ONE
-// launch for all members (the same arithmetic as scale_inputs_kernel / center_kernel).
+// hyp_stride: ls [dp] at 0 (WIDE: at TRIAL_WIDE_LS), variance at 32, noise at 33, mean at 34) -- its scaled inputs and centred
+// targets in ONE launch for all members (the same arithmetic as scale_inputs_kernel / center_kernel).
+template <bool WIDE>
 __global__ void batch_prep_kernel(const double* __restrict__ X, const double* __restrict__ Y, const double* __restrict__ hyp,
                                   int64_t hyp_stride, double* __restrict__ Xs, double* __restrict__ err, int64_t N,
                                   int64_t Npad, int d, int dp) {
@@ -39,15 +40,19 @@ __global__ void batch_prep_kernel(const double* __restrict__ X, const double* __
   if (t < Npad * dp) {
     const int64_t i = t / dp;
     const int c = (int)(t % dp);
-    Xs[(int64_t)blockIdx.y * Npad * dp + t] = (i < N && c < d) ? X[i * d + c] / h[c] : 0.0;
+    Xs[(int64_t)blockIdx.y * Npad * dp + t] = (i < N && c < d) ? X[i * d + c] / h[(WIDE ? TRIAL_WIDE_LS : 0) + c] : 0.0;
   }
   if (t < Npad) err[(int64_t)blockIdx.y * Npad + t] = (t < N) ? Y[t] - h[34] : 0.0;
 }
 void launch_batch_prep(hipStream_t s, const double* X, const double* Y, const double* hyp, int64_t hyp_stride, int B,
                        double* Xs, double* err, int64_t N, int64_t Npad, int d, int dp) {
   const int64_t n = Npad * dp;
-  hipLaunchKernelGGL(batch_prep_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, X, Y, hyp, hyp_stride,
-                     Xs, err, N, Npad, d, dp);
+  if (dp > MAX_D)
+    hipLaunchKernelGGL(batch_prep_kernel<true>, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, X, Y, hyp,
+                       hyp_stride, Xs, err, N, Npad, d, dp);
+  else
+    hipLaunchKernelGGL(batch_prep_kernel<false>, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, X, Y, hyp,
+                       hyp_stride, Xs, err, N, Npad, d, dp);
 }
 
 // K[i][j] = k(x_i, x_j) + noise * (i == j) on the N x N part; identity on the padding so that the
@@ -58,23 +63,57 @@ void launch_batch_prep(hipStream_t s, const double* X, const double* Y, const do
 // branch-free kernel_from_r2<KIND> as the sweep, so K and K* are the same function bit for bit.
 // Batched form (hyp != nullptr; tgp_nlml_trial_batch): member blockIdx.z reads its variance / noise from hyp (+ z
 // hyp_stride: slots 32, 33), its scaled inputs at Xs + z Npad DP, and writes A + z a_stride.
+// Wide form (DP == DP_WIDE, dp = dpw > MAX_D a multiple of WIDE_CHUNK): the same entries, the coordinates taken a chunk of
+// WIDE_CHUNK at a time (x_j's chunk in registers, sixteen running r^2 per lane) -- no dp-sized per-lane array.
 template <int KIND, int DP>
 __global__ __launch_bounds__(256) void assemble_K_kernel(const double* __restrict__ Xs, double* __restrict__ A,
                                                          int64_t N, int64_t Npad, double variance, double noise,
                                                          int64_t row0, const double* __restrict__ hyp = nullptr,
-                                                         int64_t hyp_stride = 0, int64_t a_stride = 0) {
+                                                         int64_t hyp_stride = 0, int64_t a_stride = 0, int dpw = 0) {
   const int64_t tj = blockIdx.x, ti = row0 / 64 + blockIdx.y;
   if (tj > ti) return;
   if (hyp) {
     const int64_t z = blockIdx.z;
     variance = hyp[z * hyp_stride + 32];
     noise = hyp[z * hyp_stride + 33];
-    Xs += z * Npad * DP;
+    Xs += z * Npad * (DP == DP_WIDE ? dpw : DP);
     A += z * a_stride;
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t j = tj * 64 + lane;
-  double xj[DP];
+  if constexpr (DP == DP_WIDE) {
+    const cptr xs = as_const(Xs);
+    const int64_t ib = ti * 64 + w * 16;   // (rows < Npad: Xs is zero padded to Npad rows)
+    double r2[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) r2[r] = 0.0;
+    for (int c0 = 0; c0 < dpw; c0 += WIDE_CHUNK) {
+      double xj[WIDE_CHUNK];
+#pragma unroll
+      for (int c = 0; c < WIDE_CHUNK; ++c) xj[c] = Xs[j * dpw + c0 + c];
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int c = 0; c < WIDE_CHUNK; ++c) {
+          const double t = xs[(ib + r) * dpw + c0 + c] - xj[c];
+          r2[r] = fma(t, t, r2[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t i = ib + r;
+      double v;
+      if (i < N && j < N) {
+        v = kernel_from_r2<KIND>(r2[r], variance);
+        if (i == j) v += noise;
+      } else {
+        v = (i == j) ? 1.0 : 0.0;
+      }
+      A[i * Npad + j] = v;
+    }
+    return;
+  }
+  double xj[DP > 0 ? DP : 1];
 #pragma unroll
   for (int c = 0; c < DP; ++c) xj[c] = Xs[j * DP + c];
   const cptr xs = as_const(Xs);
@@ -105,14 +144,15 @@ static void launch_assemble_K_dp(hipStream_t s, const double* Xs, double* A, int
   // A is addressed with GLOBAL row indices: for row0 > 0 the caller passes (scratch - row0 * Npad)
   dim3 g((unsigned)(Npad / 64), (unsigned)((Npad - row0) / 64), (unsigned)B), b(256);
 #define TGP_ASM_K(DPV) \
-  hipLaunchKernelGGL((assemble_K_kernel<KIND, DPV>), g, b, 0, s, Xs, A, N, Npad, variance, noise, row0, hyp, hyp_stride, a_stride)
+  hipLaunchKernelGGL((assemble_K_kernel<KIND, DPV>), g, b, 0, s, Xs, A, N, Npad, variance, noise, row0, hyp, hyp_stride, a_stride, dp)
   switch (dp) {
     case 2: TGP_ASM_K(2); break;
     case 4: TGP_ASM_K(4); break;
     case 6: TGP_ASM_K(6); break;
     case 8: TGP_ASM_K(8); break;
     case 16: TGP_ASM_K(16); break;
-    default: TGP_ASM_K(32); break;
+    case 32: TGP_ASM_K(32); break;
+    default: TGP_ASM_K(DP_WIDE); break;
   }
 #undef TGP_ASM_K
 }

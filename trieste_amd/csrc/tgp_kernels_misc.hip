@@ -61,7 +61,61 @@ __global__ __launch_bounds__(256) void predict_mean_wave_kernel(ModelDev m, cons
   if (lane == 0) mean[j] = acc + m.mean_const;
 }
 
+// Wide inputs (dp > MAX_D): one thread (WAVE = false) or one wave (true) per query as above, without a dp-sized array: the
+// training rows are taken WIDE_ROWS at a time (per lane), and for each group the query's coordinates a chunk of WIDE_CHUNK at
+// a time -- a chunk is scaled once per group of rows and feeds WIDE_ROWS running r^2.
+constexpr int WIDE_ROWS = 8;
+template <bool WAVE>
+__global__ __launch_bounds__(256) void predict_mean_wide_kernel(ModelDev m, const double* __restrict__ Xq, int64_t M,
+                                                                double* __restrict__ mean) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = WAVE ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (WAVE && j >= M) return;  // wave-uniform
+  const bool valid = j < M;
+  const int64_t jj = valid ? j : 0;
+  const int d = m.d, dp = m.dp;
+  const int64_t k0 = WAVE ? lane : 0, kstep = WAVE ? 64 : 1;
+  double acc = 0.0;
+  for (int64_t kb = k0; kb < m.N; kb += kstep * WIDE_ROWS) {
+    double r2[WIDE_ROWS];
+#pragma unroll
+    for (int u = 0; u < WIDE_ROWS; ++u) r2[u] = 0.0;
+    for (int c0 = 0; c0 < dp; c0 += WIDE_CHUNK) {
+      double xq[WIDE_CHUNK];
+#pragma unroll
+      for (int c = 0; c < WIDE_CHUNK; ++c) xq[c] = (c0 + c < d) ? Xq[jj * d + c0 + c] / m.ls[c0 + c] : 0.0;
+#pragma unroll
+      for (int u = 0; u < WIDE_ROWS; ++u) {
+        const int64_t k = kb + u * kstep, kk = k < m.N ? k : 0;
+#pragma unroll
+        for (int c = 0; c < WIDE_CHUNK; ++c) {
+          const double t = xq[c] - m.Xs[kk * dp + c0 + c];
+          r2[u] = fma(t, t, r2[u]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < WIDE_ROWS; ++u) {
+      const int64_t k = kb + u * kstep;
+      if (k < m.N) acc = fma(kernel_rt(m.kind, r2[u], m.variance), m.alpha[k], acc);
+    }
+  }
+  if (WAVE) {
+    acc = wave_sum(acc);
+    if (lane == 0) mean[j] = acc + m.mean_const;
+  } else if (valid) {
+    mean[j] = acc + m.mean_const;
+  }
+}
+
 void launch_predict_mean(hipStream_t s, const ModelDev& m, const double* Xq, int64_t M, double* mean) {
+  if (m.dp > MAX_D) {
+    if (M <= 32768)
+      hipLaunchKernelGGL(predict_mean_wide_kernel<true>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, m, Xq, M, mean);
+    else
+      hipLaunchKernelGGL(predict_mean_wide_kernel<false>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, m, Xq, M, mean);
+    return;
+  }
   if (M <= 32768) {
     dim3 g((unsigned)((M + 3) / 4)), b(256);
     switch (m.dp) {
@@ -348,8 +402,7 @@ __global__ __launch_bounds__(256) void penalize_kernel(double* __restrict__ vals
                                                        const double* __restrict__ scale) {
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
-  double x[MAX_D];
-  for (int c = 0; c < d; ++c) x[c] = Xq[m * d + c];
+  const double* const x = Xq + m * d;   // (any d: the coordinates are read where they are)
   double prod = 1.0;
   for (int p = 0; p < P; ++p) {
     double r2 = 0.0;
@@ -366,6 +419,35 @@ __global__ __launch_bounds__(256) void penalize_kernel(double* __restrict__ vals
 
 // value and gradient of the penalised acquisition at P' points: (a phi)' = phi a' + a phi',
 // phi' = sum_p slope_p (x - x_p) / dist_p prod_{q != p} phi_q  (O(P^2) per point; P' is a few hundred).
+// wide inputs (d > MAX_D): no d-sized arrays -- grad is scaled by phi first and a phi' is added into it one pending point at a
+// time, (a phi)' = phi a' + sum_p a w_p (x - x_p)
+__device__ void penalize_grad_wide(double* __restrict__ val, double* __restrict__ grad, const double* __restrict__ x,
+                                   int64_t m, int d, int kind, int P, const double* __restrict__ pend,
+                                   const double* __restrict__ radius, const double* __restrict__ scale) {
+  auto dist_to = [&](int p) {
+    double r2 = 0.0;
+    for (int c = 0; c < d; ++c) {
+      const double t = x[c] - pend[(int64_t)p * d + c];
+      r2 += t * t;
+    }
+    return sqrt(r2);
+  };
+  double prod = 1.0;
+  for (int p = 0; p < P; ++p) prod *= penalty_factor(kind, dist_to(p), radius[p], scale[p]);
+  const double a = val[m];
+  double* const g = grad + m * d;
+  for (int c = 0; c < d; ++c) g[c] = prod * g[c];
+  for (int p = 0; p < P; ++p) {
+    const double dist = dist_to(p);
+    double others = 1.0;
+    for (int q = 0; q < P; ++q)
+      if (q != p) others *= penalty_factor(kind, dist_to(q), radius[q], scale[q]);
+    const double w = dist > 0.0 ? penalty_slope(kind, dist, radius[p], scale[p]) * others / dist : 0.0;
+    for (int c = 0; c < d; ++c) g[c] = fma(a * w, x[c] - pend[(int64_t)p * d + c], g[c]);
+  }
+  val[m] = a * prod;
+}
+
 __global__ __launch_bounds__(64) void penalize_grad_kernel(double* __restrict__ val, double* __restrict__ grad,
                                                            const double* __restrict__ Xq, int64_t Pq, int d,
                                                            int kind, int P, const double* __restrict__ pend,
@@ -373,11 +455,13 @@ __global__ __launch_bounds__(64) void penalize_grad_kernel(double* __restrict__ 
                                                            const double* __restrict__ scale) {
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= Pq) return;
-  double x[MAX_D], gphi[MAX_D];
-  for (int c = 0; c < d; ++c) {
-    x[c] = Xq[m * d + c];
-    gphi[c] = 0.0;
+  const double* const x = Xq + m * d;
+  if (d > MAX_D) {
+    penalize_grad_wide(val, grad, x, m, d, kind, P, pend, radius, scale);
+    return;
   }
+  double gphi[MAX_D];
+  for (int c = 0; c < d; ++c) gphi[c] = 0.0;
   double prod = 1.0;
   for (int p = 0; p < P; ++p) {
     double r2 = 0.0;

@@ -64,10 +64,18 @@ constexpr int U_STAGE = UBK * ULDA + UBK * ULDB;  // doubles per stage
 // (candidate block, row group) instead of a whole block -- the group walks only its row blocks of W,
 // generates the K* rows it meets for the first time, and leaves partial (k*.alpha, sum c^2) for
 // sweep_combine_kernel (tgp_kernels_misc.hip), which runs the common tail.
+//
+// WIDE inputs (DP == DP_WIDE: dp > MAX_D, a multiple of WIDE_CHUNK, DESIGN.md 4.7): [dp][128] candidate coordinates would not fit
+// beside the two stages (2 x 52 KiB + 64 KiB at dp = 64 > 160 KiB), so they go to a per-workgroup tile in device scratch (a.xqw,
+// written once per candidate block, read back from L2 / L1 coalesced over the 128 columns) and the generating steps walk the
+// coordinates in a run-time loop.  Nothing else changes: every other step already reads K* back from the slab.
 template <int KIND, int DP, bool JOINT, bool SPLIT>
 __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
+  constexpr bool WIDE = DP == DP_WIDE;
   __shared__ __attribute__((aligned(16))) double smem[2 * U_STAGE + UBN * DP];
-  double* const xqs = smem + 2 * U_STAGE;  // [DP][128] scaled candidate coordinates
+  const int dpr = WIDE ? a.m.dp : DP;   // the padded dimension (a constant unless WIDE)
+  // [DP][128] scaled candidate coordinates
+  double* const xqs = WIDE ? a.xqw + (size_t)blockIdx.x * (size_t)dpr * UBN : smem + 2 * U_STAGE;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -106,8 +114,8 @@ __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
     const int grp = (SPLIT && ((blk / per_round) & 1)) ? ngrp - 1 - gsel : gsel;
     const int ib0 = SPLIT ? a.split_ib[grp] : 0, ib1 = SPLIT ? a.split_ib[grp + 1] : nb;
     const int T = (ib1 * (ib1 + 1) - ib0 * (ib0 + 1)) / 2 * UKSTEPS;
-    for (int e = tid; e < UBN * DP; e += 1024) {  // scale the block's candidates once (c-major)
-      const int j = e / DP, c = e % DP;
+    for (int e = tid; e < UBN * dpr; e += 1024) {  // scale the block's candidates once (c-major)
+      const int j = e / dpr, c = e % dpr;
       int64_t cand;
       if constexpr (!JOINT) {
         cand = blk * UBN + j;
@@ -148,16 +156,33 @@ __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
     auto finish_tile = [&](int buf, int ib, int kb, int ks) {
       const int64_t krow0 = (int64_t)kb * UBM + ks * UBK + 2 * krg;
       if (first_use(ib, kb) && !(TGP_EXP & 16)) {  // generate this thread's two entries (first use of the rows)
-        const cptr xs = as_const(a.m.Xs + krow0 * DP);
+        const cptr xs = as_const(a.m.Xs + krow0 * dpr);
         const cptr al = as_const(a.m.alpha + krow0);
         double r2[2] = {0.0, 0.0};
+        if constexpr (WIDE) {
+          // chunks of 8 coordinates: eight coalesced loads of the tile in flight, the two training rows by scalar loads
+          const double* const xw = xqs + kcol;
+          for (int c0 = 0; c0 < dpr; c0 += 8) {
+            double x[8];
 #pragma unroll
-        for (int c = 0; c < DP; ++c) {
-          const double x = xqs[c * UBN + kcol];
+            for (int u = 0; u < 8; ++u) x[u] = xw[(c0 + u) * UBN];
 #pragma unroll
-          for (int r = 0; r < 2; ++r) {
-            const double t0 = x - xs[r * DP + c];
-            r2[r] = fma(t0, t0, r2[r]);
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+              for (int r = 0; r < 2; ++r) {
+                const double t0 = x[u] - xs[r * dpr + c0 + u];
+                r2[r] = fma(t0, t0, r2[r]);
+              }
+          }
+        } else {
+#pragma unroll
+          for (int c = 0; c < DP; ++c) {
+            const double x = xqs[c * UBN + kcol];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+              const double t0 = x - xs[r * DP + c];
+              r2[r] = fma(t0, t0, r2[r]);
+            }
           }
         }
 #pragma unroll
@@ -378,10 +403,17 @@ __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
           if (g >= a.G) continue;
           const int ca = gi * q + aa, cb = gi * q + bb;  // columns inside the half
           double r2 = 0.0;
+          if constexpr (WIDE) {
+            for (int c = 0; c < dpr; ++c) {
+              const double tt = xqs[c * UBN + hh * 64 + ca] - xqs[c * UBN + hh * 64 + cb];
+              r2 = fma(tt, tt, r2);
+            }
+          } else {
 #pragma unroll
-          for (int c = 0; c < DP; ++c) {
-            const double tt = xqs[c * UBN + hh * 64 + ca] - xqs[c * UBN + hh * 64 + cb];
-            r2 = fma(tt, tt, r2);
+            for (int c = 0; c < DP; ++c) {
+              const double tt = xqs[c * UBN + hh * 64 + ca] - xqs[c * UBN + hh * 64 + cb];
+              r2 = fma(tt, tt, r2);
+            }
           }
           double cv = kernel_from_r2<KIND>(r2, variance) - Sg[hh * 4096 + ca * 64 + cb];
           if (aa == bb) cv = fmax(cv, VAR_FLOOR);  // reference interface.py:130-132
@@ -444,7 +476,10 @@ hipError_t launch_sweep_dp(hipStream_t s, const SweepArgs& a, int64_t grid) {
     case 8: hipLaunchKernelGGL((sweep_kernel<KIND, 8, JOINT, SPLIT>), g, b, 0, s, a); break;
     case 16: hipLaunchKernelGGL((sweep_kernel<KIND, 16, JOINT, SPLIT>), g, b, 0, s, a); break;
     case 32: hipLaunchKernelGGL((sweep_kernel<KIND, 32, JOINT, SPLIT>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
+    default:
+      if (a.m.dp <= MAX_D || a.m.dp % WIDE_CHUNK != 0 || !a.xqw) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((sweep_kernel<KIND, DP_WIDE, JOINT, SPLIT>), g, b, 0, s, a);
+      break;
   }
   return hipGetLastError();
 }

@@ -42,6 +42,8 @@ class _Arg:
 
 class GPEngine:
     def __init__(self, d: int, kernel: str = "matern52", device: int = 0):
+        """An exact-GPR engine on ``device`` for inputs of ``d`` dimensions, 1 <= d <= 1024 (``_lib.MAX_D``).  Above 32
+        dimensions the sweeps run in float64 only (the int8 precisions are refused) and trajectories are refused."""
         self._lib = _lib.load()
         if kernel not in _lib.KERNELS:
             raise ValueError(f"unknown kernel {kernel!r}; choose from {sorted(_lib.KERNELS)}")

@@ -636,8 +636,12 @@ class GaussianProcessRegression:
 
     def trajectory_sampler(self):
         """models.py:323-345: decoupled sampler by default, the RFF weight-posterior sampler otherwise."""
+        from ._lib import NARROW_MAX_D
         from .sampler import DecoupledTrajectorySampler, RandomFourierFeatureTrajectorySampler
 
+        d = self._model.data[0].shape[1]
+        if d > NARROW_MAX_D:
+            raise ValueError(f"trajectory samplers support input dimensions up to {NARROW_MAX_D}, got {d}")
         if self._use_decoupled_sampler:
             return DecoupledTrajectorySampler(self, self._num_rff_features)
         return RandomFourierFeatureTrajectorySampler(self, self._num_rff_features)
