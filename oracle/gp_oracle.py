@@ -27,6 +27,7 @@ Pinning status (see DESIGN.md "Oracle"):
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -55,6 +56,37 @@ def scaled_square_dist(X: np.ndarray, X2: np.ndarray, lengthscales: np.ndarray) 
     As = np.sum(A * A, axis=-1)[..., :, None]
     Bs = np.sum(B * B, axis=-1)[..., None, :]
     return As + Bs - 2.0 * np.matmul(A, np.swapaxes(B, -1, -2))
+
+
+def difference_form_sq_dist(X: np.ndarray, X2: np.ndarray, lengthscales: np.ndarray) -> np.ndarray:
+    """r^2 = sum_c (a_c - b_c)^2 of the scaled inputs a = x / ls, b = x2 / ls -- the engine's form.  Its rounding error is
+    relative to r^2 itself (exact 0 at coincident points), where the dot-product form of ``scaled_square_dist`` errs by
+    about eps (|a|^2 + |b|^2): on inputs far from the origin (a box [1024, 1025]^d) that swamps the distances.  In row
+    chunks to bound the memory."""
+    A, B = np.asarray(X, dtype=np.float64) / lengthscales, np.asarray(X2, dtype=np.float64) / lengthscales
+    if A.ndim != 2 or B.ndim != 2:
+        return np.sum((A[..., :, None, :] - B[..., None, :, :]) ** 2, axis=-1)
+    out = np.empty((A.shape[0], B.shape[0]))
+    rows = max(1, (1 << 24) // max(1, B.size))
+    for i in range(0, A.shape[0], rows):
+        out[i:i + rows] = np.sum((A[i:i + rows, None, :] - B[None, :, :]) ** 2, axis=-1)
+    return out
+
+
+@contextlib.contextmanager
+def difference_form():
+    """Run every oracle function with r^2 in the difference form (``difference_form_sq_dist``) inside the block.
+
+    ``kernel_matrix`` is the only place the oracle forms K or K*, and it looks ``scaled_square_dist`` up at call time,
+    so swapping that name is enough; the gradient functions take differences already.  The default stays gpflow's
+    dot-product form (the goldens and the unit-cube parity tests are written against it).  Not thread-safe."""
+    global scaled_square_dist
+    saved = scaled_square_dist
+    scaled_square_dist = difference_form_sq_dist
+    try:
+        yield
+    finally:
+        scaled_square_dist = saved
 
 
 def kernel_from_r2(kind: str, variance: float, r2: np.ndarray) -> np.ndarray:

@@ -23,18 +23,6 @@ CONFIGS = [
 VARIANT_FUSED, VARIANT_SPLIT, VARIANT_SWEEP_SMALL = 1, 2, 1024
 
 
-def _difference_form_sq_dist(X, X2, lengthscales):
-    """r^2 = sum_c (a_c - b_c)^2 of the scaled inputs (the engine's form), in row chunks to bound the memory."""
-    A, B = np.asarray(X) / lengthscales, np.asarray(X2) / lengthscales
-    if A.ndim != 2 or B.ndim != 2:
-        return np.sum((A[..., :, None, :] - B[..., None, :, :]) ** 2, axis=-1)
-    out = np.empty((A.shape[0], B.shape[0]))
-    rows = max(1, (1 << 24) // max(1, B.size))
-    for i in range(0, A.shape[0], rows):
-        out[i:i + rows] = np.sum((A[i:i + rows, None, :] - B[None, :, :]) ** 2, axis=-1)
-    return out
-
-
 @pytest.fixture(autouse=True)
 def _matern12_oracle_in_difference_form(request, monkeypatch):
     """For Matern-1/2 the oracle's squared distances are taken in the difference form.
@@ -48,7 +36,7 @@ def _matern12_oracle_in_difference_form(request, monkeypatch):
     callspec = getattr(request.node, "callspec", None)
     cfg = callspec.params.get("cfg") if callspec is not None else None
     if cfg is not None and cfg[3] == "matern12":
-        monkeypatch.setattr(O, "scaled_square_dist", _difference_form_sq_dist)
+        monkeypatch.setattr(O, "scaled_square_dist", O.difference_form_sq_dist)
 
 
 def _engine(kind, d, variance, ls, noise, c, X, Y, variant=0):

@@ -82,6 +82,7 @@ ModelDev model_dev(tgp_handle h) {
   m.mean_const = h->mean_const;
   m.ls = h->d_ls.as<double>();
   m.Xs = h->d_Xs.as<double>();
+  m.xc = h->d_xc.as<double>();
   m.xn = h->d_xn.as<double>();
   m.Wt = h->d_A.as<double>();  // A is recycled as Wt after the factorisation
   m.alpha = h->d_alpha.as<double>();
@@ -333,10 +334,10 @@ hipError_t launch_sweep_i8_timed(tgp_handle h, SweepArgs& am) {
     if ((e = h->d_wq.reserve((size_t)planes * Npad * Npad)) != hipSuccess) return e;
     if ((e = h->d_rs.reserve((size_t)2 * Npad * sizeof(double))) != hipSuccess) return e;
     launch_w_digits(h->stream, h->d_W.as<double>(), h->N, Npad, h->d_rs.as<double>(), h->d_wq.p, planes);
-    if (h->dp <= 16) {   // the generating steps' training rows as DMA-able tiles
+    if (h->dp <= 16) {   // the generating steps' training rows as DMA-able tiles, centred (ModelDev::xc)
       const int xt = i8_xs_tile_doubles(h->dp);
       if ((e = h->d_xsa.reserve((size_t)(Npad / 32) * xt * sizeof(double))) != hipSuccess) return e;
-      launch_xs_tiles(h->stream, h->d_Xs.as<double>(), h->d_alpha.as<double>(), Npad, h->dp, xt, h->d_xsa.as<double>());
+      launch_xs_tiles(h->stream, h->d_xc.as<double>(), h->d_alpha.as<double>(), Npad, h->dp, xt, h->d_xsa.as<double>());
     }
     h->wq_version = h->data_version;
     h->wq_planes = planes;
@@ -1024,7 +1025,7 @@ int tgp_destroy(tgp_handle h) {
   } else if (h->stream == nullptr) {
     (void)hipStreamSynchronize(nullptr);
   }
-  for (DevBuf* b : {&h->d_xn, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
+  for (DevBuf* b : {&h->d_xc, &h->d_xn, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
                     &h->d_err, &h->d_tmp1, &h->d_tmp2, &h->d_info, &h->d_pen, &h->d_ent, &h->d_repv, &h->d_wq, &h->d_rs, &h->d_xsa, &h->s_ent, &h->s_in, &h->s_in2, &h->s_out1,
                     &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_xqw, &h->s_rep,
                     &h->s_rep_stats, &h->d_dag_flags, &h->d_dag_trace})
@@ -1218,6 +1219,7 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
   const size_t nn = (size_t)Npad * Npad * sizeof(double);
   const int d = h->d, dp = h->dp;
   HIPCHK(h, h->d_Xs.reserve((size_t)Npad * dp * sizeof(double)));
+  HIPCHK(h, h->d_xc.reserve((size_t)Npad * dp * sizeof(double)));
   HIPCHK(h, h->d_xn.reserve((size_t)Npad * sizeof(double)));
   if (keep_rows == 0) {
     HIPCHK(h, h->d_A.reserve(nn));
@@ -1237,7 +1239,7 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
   double* L = h->d_L.as<double>();
   double* W = h->d_W.as<double>();
   launch_scale_inputs(s, h->d_X.as<double>(), h->d_ls.as<double>(), h->d_Xs.as<double>(), N, Npad, d, dp);
-  launch_row_norms(s, h->d_Xs.as<double>(), h->d_xn.as<double>(), Npad, dp);
+  launch_centred_rows(s, h->d_Xs.as<double>(), h->d_xc.as<double>(), h->d_xn.as<double>(), Npad, dp);
   if (keep_rows == 0) {
     launch_assemble_K(s, h->d_Xs.as<double>(), A, N, Npad, dp, h->kind, h->variance, h->noise);
     if (h->zeroed_L != L || h->zeroed_W != W || h->zeroed_npad != Npad) {
@@ -1697,6 +1699,7 @@ int tgp_clone_from(tgp_handle dst, tgp_handle src) {
     HIPCHK(dst, copy(dst->d_X, src->d_X, N * src->d * sizeof(double)));
     HIPCHK(dst, copy(dst->d_Y, src->d_Y, N * sizeof(double)));
     HIPCHK(dst, copy(dst->d_Xs, src->d_Xs, Npad * src->dp * sizeof(double)));
+    HIPCHK(dst, copy(dst->d_xc, src->d_xc, Npad * src->dp * sizeof(double)));
     HIPCHK(dst, copy(dst->d_xn, src->d_xn, Npad * sizeof(double)));
     HIPCHK(dst, copy(dst->d_A, src->d_A, nn));
     HIPCHK(dst, copy(dst->d_L, src->d_L, nn));

@@ -33,7 +33,10 @@ struct ModelDev {       // device-resident model state (all pointers device)
   double variance, noise, mean_const;
   const double* ls;     // [dp] lengthscales padded with 1.0
   const double* Xs;     // [Npad][dp]  X / ls, zero padded
-  const double* xn;     // [Npad] |Xs_k|^2 (dot-product form of the distances in the trajectory kernel)
+  const double* xc;     // [Npad][dp]  Xs - Xs_0: the scaled inputs centred at the first training input
+  const double* xn;     // [Npad] |xc_k|^2.  The dot-product form of the distances (int8 sweep, trajectories) works on
+                        // centred coordinates: its rounding error is eps (|x|^2 + |X_k|^2), which on uncentred inputs grows
+                        // with (offset / lengthscale)^2 and swamps the distances on a box far from the origin
   const double* Wt;     // [Npad][Npad] Wt[k][i] = (L^-1)[i][k], zero outside the N x N lower part
   const double* alpha;  // [Npad] K^-1 (Y - c), zero padded
 };
@@ -123,7 +126,7 @@ void launch_cov_sym_tail(hipStream_t s, const ModelDev& m, const double* X, int6
                          double jitter, double* A);
 void launch_pad_copy(hipStream_t s, const double* src, int64_t r, int64_t c, double* dst, int64_t rp, int64_t cp);
 void launch_sample_tail(hipStream_t s, const double* mean, const double* R, int64_t n, int S, int64_t Sp, double* out);
-void launch_row_norms(hipStream_t s, const double* Xs, double* xn, int64_t Npad, int dp);
+void launch_centred_rows(hipStream_t s, const double* Xs, double* xc, double* xn, int64_t Npad, int dp);
 // y[i] = sum_k M[i][k] x[k] over k in [klo(i), khi(i)] ; lower: k<=i ; upper: k>=i
 void launch_trmv(hipStream_t s, const double* Mx, int64_t ld, int64_t n, const double* x, double* y,
                  bool lower);

@@ -846,15 +846,21 @@ void launch_center(hipStream_t s, const double* Y, double c, double* err, int64_
                      Npad);
 }
 
-__global__ void row_norms_kernel(const double* __restrict__ Xs, double* __restrict__ xn, int64_t Npad, int dp) {
+// xc = Xs - Xs_0 (row 0: the first training input) and xn = |xc_k|^2, for the dot-product form of the distances
+__global__ void centred_rows_kernel(const double* __restrict__ Xs, double* __restrict__ xc, double* __restrict__ xn,
+                                    int64_t Npad, int dp) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= Npad) return;
   double s = 0.0;
-  for (int c = 0; c < dp; ++c) s = fma(Xs[t * dp + c], Xs[t * dp + c], s);
+  for (int c = 0; c < dp; ++c) {
+    const double v = Xs[t * dp + c] - Xs[c];
+    xc[t * dp + c] = v;
+    s = fma(v, v, s);
+  }
   xn[t] = s;
 }
-void launch_row_norms(hipStream_t s, const double* Xs, double* xn, int64_t Npad, int dp) {
-  hipLaunchKernelGGL(row_norms_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, s, Xs, xn, Npad, dp);
+void launch_centred_rows(hipStream_t s, const double* Xs, double* xc, double* xn, int64_t Npad, int dp) {
+  hipLaunchKernelGGL(centred_rows_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, s, Xs, xc, xn, Npad, dp);
 }
 
 // one wave per row: y[i] = sum_{k in tri range} M[i][k] x[k].  The row is walked from a 16-byte aligned start

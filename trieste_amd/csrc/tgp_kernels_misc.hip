@@ -1005,7 +1005,8 @@ void launch_w_digits(hipStream_t s, const double* W, int64_t N, int64_t Npad, do
 }
 
 // The training rows of the int8 sweep's generating steps as DMA-able tiles (tgp_kernels_sweep_i8.inc): tile t =
-// [32 rows of Xs][dp], alpha[32], |row|^2 [32], zero padded to xt doubles (whole KiB).
+// [32 rows of Xs][dp], alpha[32], |row|^2 [32], zero padded to xt doubles (whole KiB).  The launch passes the centred rows
+// (ModelDev::xc): the kernel subtracts Xs_0 from its candidates to match.
 __global__ __launch_bounds__(256) void xs_tiles_kernel(const double* __restrict__ Xs, const double* __restrict__ alpha, int dp, int xt,
                                                        double* __restrict__ out) {
   const int64_t tile = blockIdx.x;

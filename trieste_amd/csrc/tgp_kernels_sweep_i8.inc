@@ -256,7 +256,8 @@ __global__ __launch_bounds__(512, 2) void sweep_i8_kernel(const SweepArgs a) {
       const int j = e / DP, c = e % DP;
       const int64_t cand = blk * I8_BN + j;
       const int64_t src = cand < a.M ? cand : 0;
-      xqs[c * I8_BN + j] = (c < d) ? a.Xq[src * d + c] / as_const(a.m.ls)[c] : 0.0;
+      // with the staged tiles (ModelDev::xc) the coordinates are centred at the first training input, Xs_0
+      xqs[c * I8_BN + j] = (c < d) ? a.Xq[src * d + c] / as_const(a.m.ls)[c] - (xs_lds ? as_const(a.m.Xs)[c] : 0.0) : 0.0;
     }
     v16i acc[2][I8_NS];
 #pragma unroll

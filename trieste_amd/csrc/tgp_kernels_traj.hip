@@ -56,12 +56,8 @@ __global__ __launch_bounds__(256) void traj_eval_kernel(TrajDev t, const double*
   const bool valid = item < nitems;
   const int myb = PER_TRAJ ? (int)(item % B) : 0;
   double xq[DP];
-  double nb = 0.0;
 #pragma unroll
-  for (int c = 0; c < DP; ++c) {
-    xq[c] = (c < d && valid) ? Xq[item * d + c] / as_const(t.m.ls)[c] : 0.0;
-    nb = fma(xq[c], xq[c], nb);
-  }
+  for (int c = 0; c < DP; ++c) xq[c] = (c < d && valid) ? Xq[item * d + c] / as_const(t.m.ls)[c] : 0.0;
   double acc[BP];
 #pragma unroll
   for (int b = 0; b < BP; ++b) acc[b] = 0.0;
@@ -84,9 +80,17 @@ __global__ __launch_bounds__(256) void traj_eval_kernel(TrajDev t, const double*
     }
   }
   if (rff_only == 0 || rff_only == 3) {
-    const cptr xs = as_const(t.m.Xs);
+    // the canonical part on coordinates centred at the first training input (ModelDev::xc; the RFF phase above is not
+    // translation invariant and takes the uncentred ones)
+    const cptr xs = as_const(t.m.xc);
     const cptr xn = as_const(t.m.xn);
     const cptr vv = as_const(t.v);
+    double nb = 0.0;
+#pragma unroll
+    for (int c = 0; c < DP; ++c) {
+      xq[c] -= as_const(t.m.Xs)[c];
+      nb = fma(xq[c], xq[c], nb);
+    }
     constexpr double SC = TrajShape<KIND>::SCALE;
     const double nbs = SC * nb;
     double acck[BP];  // sum_k shape_k v[k][b]: the variance multiplies it once, below
