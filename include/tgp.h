@@ -258,6 +258,23 @@ int tgp_sample_box(tgp_handle h, uint64_t seed, int64_t first, int64_t M, const 
 int tgp_qei(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S, double eta,
             double jitter, double* out, int where);
 
+/* ---- analytic batch EI ------------------------------------------------------------------- */
+/* == batch_expected_improvement.__call__ (function.py:1747-1805): the Chevalier-Ginsbourger closed form of the multi-point
+ * expected improvement (_compute_batch_expected_improvement, function.py:1651-1745), its q CDFs of dimension q and q^2 CDFs
+ * of dimension q - 1 estimated by MultivariateNormalCDF (function/utils.py:109-199: Genz's sequential conditioning on fixed
+ * Sobol points).  Xq [G,q,d]; w1 [S,q] and w2 [S,q-1] the Sobol points of the two CDF sizes in [0,1) (host or device like
+ * Xq); out [G].  The reference's constants are built in: cov + 1e-6 I before the closed form (function.py:1776-1783), another
+ * 1e-6 I inside every CDF's factorisation (utils.py:114, 143-144), 1e-12 on the factor's diagonal, the quantile's argument
+ * kept in [1e-6, 1 - 1e-6] (utils.py:177).  The value is NOT clipped at zero.  2 <= q <= 16 (q = 1 is an error in the
+ * reference as well: MultivariateNormalCDF(dim = 0)), S >= 1, else TGP_ERR_SHAPE / TGP_ERR_ARG; TGP_ERR_NOT_PD names the
+ * first group one of whose factorisations met a non-positive pivot.  Value only: no gradient behind this entry yet.
+ *   tgp_batch_ei_moments: the same tail on caller-supplied moments, mean [G,q] and cov [G,q,q] AS THE MODEL RETURNS THEM
+ *     (the entry applies the 1e-6 and the change of sign itself); needs no data on the handle. */
+int tgp_batch_ei(tgp_handle h, const double* Xq, int64_t G, int q, const double* w1, const double* w2, int S,
+                 double eta, double* out, int where);
+int tgp_batch_ei_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                         const double* w2, int S, double eta, double* out, int where);
+
 /* == BatchReparametrizationSampler.sample (sampler.py:208-287) itself: out [G,S,q] = mean +
  * (chol(cov + jitter*I) eps)^T for Xq [G,q,d], eps [q,S].  q <= 64. */
 int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S,

@@ -5,9 +5,11 @@ MultipleOptimismNegativeLowerConfidenceBound / PredictiveVariance / ExpectedCons
 :mod:`trieste_amd.extras`; this package exports SURVEY section 8 rows only."""
 from .continuous_thompson_sampling import (GreedyContinuousThompsonSampling, ParallelContinuousThompsonSampling,
                                            negate_trajectory_function)
-from .function import (AugmentedExpectedImprovement, BatchMonteCarloExpectedImprovement, ExpectedImprovement,
+from .function import (AugmentedExpectedImprovement, BatchExpectedImprovement, BatchMonteCarloExpectedImprovement,
+                       ExpectedImprovement,
                        MonteCarloExpectedImprovement, NegativeLowerConfidenceBound, ProbabilityOfImprovement,
-                       augmented_expected_improvement, batch_monte_carlo_expected_improvement, expected_improvement,
+                       augmented_expected_improvement, batch_expected_improvement,
+                       batch_monte_carlo_expected_improvement, expected_improvement,
                        monte_carlo_expected_improvement, negative_lower_confidence_bound,
                        probability_below_threshold)
 from .greedy_batch import (Fantasizer, LocalPenalization, PenalizedAcquisition, hard_local_penalizer,

@@ -1,6 +1,7 @@
 """Acquisition functions of the hot path (reference trieste/acquisition/function/function.py):
 ExpectedImprovement / expected_improvement (96-223), BatchMonteCarloExpectedImprovement /
-batch_monte_carlo_expected_improvement (1074-1186), plus the sibling tails on the same posterior
+batch_monte_carlo_expected_improvement (1074-1186), BatchExpectedImprovement / batch_expected_improvement (1189-1805: the
+analytic multi-point EI), plus the sibling tails on the same posterior
 ProbabilityOfImprovement (481-515, "probability_below_threshold"), NegativeLowerConfidenceBound
 (328-418), AugmentedExpectedImprovement (226-325) and MonteCarloExpectedImprovement (786-920).  Values are computed by libtgp's fused kernels; the objects also expose the fused
 device arg-max / top-k used by :mod:`trieste_amd.acquisition.optimizer`.
@@ -12,6 +13,7 @@ from typing import Optional
 import numpy as np
 
 from ..data import Dataset
+from ..rng import make_rng
 from ..sampler import JITTER
 from .interface import (AcquisitionFunctionBuilder, AcquisitionFunctionClass, SingleModelAcquisitionBuilder,
                         SingleModelVectorizedAcquisitionBuilder)
@@ -360,6 +362,99 @@ class BatchMonteCarloExpectedImprovement(SingleModelAcquisitionBuilder):
     def update_acquisition_function(self, function, model, dataset: Optional[Dataset] = None):
         if not isinstance(function, batch_monte_carlo_expected_improvement):
             raise ValueError("function must be a batch_monte_carlo_expected_improvement instance")
+        function.update(_eta_from(model, dataset))
+        return function
+
+
+SOBOL_SKIP_BOUND = 1 << 20
+
+
+def sobol_points(num_samples: int, dim: int, skip: int) -> np.ndarray:
+    """``num_samples`` points of the unscrambled Sobol sequence of dimension ``dim`` in [0, 1), the first ``skip`` skipped
+    -> [num_samples, dim] (``tf.math.sobol_sample``, whose stream starts after the all-zero point: hence the ``+ 1``, as in
+    :func:`trieste_amd.sampler.qmc_normal_samples`)."""
+    import warnings
+
+    from scipy.stats import qmc
+
+    gen = qmc.Sobol(d=dim, scramble=False)
+    gen.fast_forward(int(skip) + 1)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # scipy warns when num_samples is not a power of two
+        return np.ascontiguousarray(gen.random(num_samples), dtype=np.float64)
+
+
+class batch_expected_improvement(AcquisitionFunctionClass):
+    """The analytic multi-point expected improvement of Chevalier and Ginsbourger, its multivariate normal CDFs estimated
+    with Genz's sequential conditioning on fixed Sobol points (function.py:1281-1805, function/utils.py:29-199).  Posterior
+    and tail run on the device (``trieste_amd.engine.batch_ei``); 2 <= q <= 16 points per batch; value only (no
+    ``value_and_gradient`` yet: ``batchify_joint`` optimizes it by random search).
+
+    ``jitter`` is kept and, as in the reference, never applied: ``__call__`` adds a hard-coded 1e-6 to the covariance
+    (function.py:1776-1783) and every CDF another 1e-6 (utils.py:114).
+
+    The Sobol skip is ONE number for both CDF sizes (function.py:1756-1770), redrawn by :meth:`update`.  The reference draws
+    it below 10^9; scipy's ``fast_forward`` is linear in the skip (seconds at 10^9), so it is drawn below 2^20 here, from
+    the package's seeded generator (:func:`trieste_amd.rng.set_seed`) -- the skip only decorrelates successive steps."""
+
+    def __init__(self, sample_size: int, model, eta, jitter: float):
+        self._sample_size = sample_size
+        self._jitter = jitter
+        self._model = model
+        self._engine = _require_engine(model, type(self).__name__)
+        self._eta = float(np.asarray(eta).reshape(()))
+        self._rng = make_rng()
+        self._points = {}   # q -> (w1 [S, q], w2 [S, q - 1]) of the current skip
+        self._num_sobol_skip = int(self._rng.integers(SOBOL_SKIP_BOUND))
+
+    def update(self, eta) -> None:
+        """New eta and a new Sobol skip (function.py:1308-1313)."""
+        self._eta = float(np.asarray(eta).reshape(()))
+        self._num_sobol_skip = int(self._rng.integers(SOBOL_SKIP_BOUND))
+        self._points = {}
+
+    def sobol(self, q: int):
+        """(w1 [S, q], w2 [S, q - 1]): the points of the q- and (q - 1)-dimensional CDFs at the current skip."""
+        if q not in self._points:
+            self._points[q] = (sobol_points(self._sample_size, q, self._num_sobol_skip),
+                               sobol_points(self._sample_size, q - 1, self._num_sobol_skip))
+        return self._points[q]
+
+    def __call__(self, x):
+        """x [..., q, D] -> [..., 1]."""
+        from ..engine import BATCH_EI_MAX_Q, batch_ei
+
+        if not _is_torch(x):
+            x = np.asarray(x, dtype=np.float64)
+        if len(x.shape) < 2:
+            raise ValueError(f"x must be [..., q, D], got shape {tuple(x.shape)}")
+        q = int(x.shape[-2])
+        if not 2 <= q <= BATCH_EI_MAX_Q:  # (q = 1 fails in the reference too: MultivariateNormalCDF(dim=0), utils.py:51)
+            raise ValueError(f"BatchExpectedImprovement takes batches of 2 to {BATCH_EI_MAX_Q} points, got {q}")
+        w1, w2 = self.sobol(q)
+        return batch_ei(self._engine, x, w1, w2, self._eta)[..., None]
+
+
+class BatchExpectedImprovement(SingleModelAcquisitionBuilder):
+    """Builder for the analytic batch EI (function.py:1189-1278); eta = min posterior mean at the observed points."""
+
+    def __init__(self, sample_size: int, *, jitter: float = JITTER):
+        if sample_size <= 0:
+            raise ValueError(f"sample_size must be positive, got {sample_size}")
+        if jitter < 0:
+            raise ValueError(f"jitter must be non-negative, got {jitter}")
+        self._sample_size = sample_size
+        self._jitter = jitter
+
+    def __repr__(self) -> str:
+        return f"BatchExpectedImprovement({self._sample_size!r}, jitter={self._jitter!r})"
+
+    def prepare_acquisition_function(self, model, dataset: Optional[Dataset] = None):
+        return batch_expected_improvement(self._sample_size, model, _eta_from(model, dataset), self._jitter)
+
+    def update_acquisition_function(self, function, model, dataset: Optional[Dataset] = None):
+        if not isinstance(function, batch_expected_improvement):
+            raise ValueError("function must be a batch_expected_improvement instance")
         function.update(_eta_from(model, dataset))
         return function
 

@@ -2531,6 +2531,107 @@ int tgp_qei(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps,
   return TGP_OK;
 }
 
+// ---- analytic batch EI: tgp_qei's body with bei_tail_kernel behind the joint posterior -----------------------------------------
+static int bei_check(tgp_handle h, int q, const double* w1, const double* w2, int S) {
+  if (q < 2 || q > BEI_MAX_Q) return fail(h, TGP_ERR_SHAPE, "batch EI: q must be in 2..%d, got %d", BEI_MAX_Q, q);
+  if (S < 1 || !w1 || !w2) return fail(h, TGP_ERR_ARG, "batch EI: need S >= 1 Sobol points of both sizes");
+  return TGP_OK;
+}
+// w1 [S][q] and w2 [S][q-1] behind each other in one staging buffer
+static int bei_stage_points(tgp_handle h, int q, const double* w1, const double* w2, int S, int where, const double** d1,
+                            const double** d2) {
+  if (where == TGP_DEVICE) {
+    *d1 = w1;
+    *d2 = w2;
+    return TGP_OK;
+  }
+  const size_t n1 = (size_t)S * q, n2 = (size_t)S * (q - 1);
+  HIPCHK(h, h->s_in2.reserve((n1 + n2) * sizeof(double)));
+  double* const p = h->s_in2.as<double>();
+  HIPCHK(h, hipMemcpyAsync(p, w1, n1 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p + n1, w2, n2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  *d1 = p;
+  *d2 = p + n1;
+  return TGP_OK;
+}
+static int bei_finish(tgp_handle h) {
+  int info = 0;
+  HIPCHK(h, hipMemcpy(&info, h->d_info.p, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipGetLastError());
+  if (info != 0)
+    return fail(h, TGP_ERR_NOT_PD, "batch EI: a covariance of group %d is not positive definite (after the 1e-6 jitters)",
+                info - 1);
+  return TGP_OK;
+}
+
+int tgp_batch_ei(tgp_handle h, const double* Xq, int64_t G, int q, const double* w1, const double* w2, int S, double eta,
+                 double* out, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = bei_check(h, q, w1, w2, S)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!out) return fail(h, TGP_ERR_ARG, "out is NULL");
+  const double* dXq;
+  double *dmean, *dcov;
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));  // (tgp_qei's rule)
+  if (int rc = set_device(h)) return rc;
+  const double *dw1, *dw2;
+  if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
+  HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  double total_ms = 0.0;
+  int launches = 0;
+  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
+    const int64_t gc = std::min(chunk, G - g0);
+    if (int rc = joint_common(h, Xq + g0 * q * h->d, gc, q, where, &dXq, &dmean, &dcov, nullptr, nullptr, true))
+      return rc;
+    double* dout;
+    if (int rc = stage_out_prepare(h, h->s_out3, out + g0, gc, where, &dout)) return rc;
+    launch_bei_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, dout, h->d_info.as<int>());
+    if (int rc = stage_out_finish(h, dout, out + g0, gc, where)) return rc;
+    if (int rc = sync(h)) return rc;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;  // (the posterior part, as tgp_qei reports it)
+    ++launches;
+  }
+  h->last_ms = total_ms;
+  h->last_launches = launches;
+  return bei_finish(h);
+}
+
+int tgp_batch_ei_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                         const double* w2, int S, double eta, double* out, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = bei_check(h, q, w1, w2, S)) return rc;
+  if (G < 0 || (G > 0 && (!mean || !cov || !out))) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (G == 0) return TGP_OK;
+  if (int rc = set_device(h)) return rc;
+  const double *dw1, *dw2, *dmean, *dcov;
+  if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
+  HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
+  double total_ms = 0.0;
+  int launches = 0;
+  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
+    const int64_t gc = std::min(chunk, G - g0);
+    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, (size_t)gc * q, where, &dmean)) return rc;
+    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, (size_t)gc * q * q, where, &dcov)) return rc;
+    double* dout;
+    if (int rc = stage_out_prepare(h, h->s_out3, out + g0, gc, where, &dout)) return rc;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // here the events bracket the tail itself
+    launch_bei_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, dout, h->d_info.as<int>());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    if (int rc = stage_out_finish(h, dout, out + g0, gc, where)) return rc;
+    if (int rc = sync(h)) return rc;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;
+    ++launches;
+  }
+  h->last_ms = total_ms;
+  h->last_launches = launches;
+  return bei_finish(h);
+}
+
 int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S,
                         double jitter, double* out, int where) {
   if (!h) return TGP_ERR_ARG;

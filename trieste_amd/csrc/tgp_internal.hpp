@@ -159,6 +159,10 @@ void launch_qei_tail(hipStream_t s, const double* mean, const double* cov, int64
 size_t qei_grad_tail_lds_bytes(int q, int S);
 void launch_qei_grad_tail(hipStream_t s, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
                           double eta, double jitter, double* val, double* gmean, double* gcov, int* info);
+// the analytic multi-point EI (tgp_kernels_bei.hip): 2 <= q <= BEI_MAX_Q, w1 [S][q], w2 [S][q - 1]
+constexpr int BEI_MAX_Q = 16;
+void launch_bei_tail(hipStream_t s, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                     const double* w2, int S, double eta, double* out, int* info);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

@@ -676,3 +676,65 @@ class Trajectory:
         self._eng._chk(self._eng._lib.tgp_traj_argmin(self._t, a.ptr, a.shape[0], int(index_base),
                                                       vals.ctypes.data, idx.ctypes.data, a.where))
         return vals, idx
+
+
+# -- analytic batch EI (tgp_batch_ei / tgp_batch_ei_moments) ---------------------------------------------------------------
+# Module-level functions, not methods: an object that brings its own ``batch_ei`` / ``batch_ei_moments`` (a stand-in engine
+# of the host-logic tests) is deferred to; a :class:`GPEngine` goes to the library.
+BATCH_EI_MAX_Q = 16
+
+
+def _sobol_args(a: _Arg, q: int, w1, w2):
+    """The two Sobol point sets [S, q] and [S, q - 1], brought to where the first argument lives."""
+    if a.where == _lib.DEVICE:
+        import torch
+
+        w1, w2 = (w if _is_torch(w) and w.is_cuda else torch.as_tensor(np.ascontiguousarray(w, dtype=_NP)).to(a.device)
+                  for w in (w1, w2))
+    elif any(_is_torch(w) and w.is_cuda for w in (w1, w2)):
+        raise ValueError("the Sobol points are on the device but the first argument is a host array")
+    p1, p2 = _Arg(w1), _Arg(w2)
+    S = p1.shape[0] if len(p1.shape) == 2 else -1
+    if p1.shape != (S, q) or p2.shape != (S, q - 1):
+        raise ValueError(f"w1 must be [S, {q}] and w2 [S, {q - 1}], got {p1.shape} and {p2.shape}")
+    return p1, p2, S
+
+
+def batch_ei(engine, Xq, w1, w2, eta: float):
+    """Xq [..., q, d] (2 <= q <= 16), Sobol points w1 [S, q] and w2 [S, q - 1] in [0, 1) -> [...]: the analytic multi-point
+    expected improvement of every q-batch (reference ``batch_expected_improvement.__call__``), posterior and tail on the
+    device (tgp_batch_ei).  Value only."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei"):
+        return engine.batch_ei(Xq, w1, w2, eta)
+    a = _Arg(Xq)
+    if len(a.shape) < 2 or a.shape[-1] != engine.d:
+        raise ValueError(f"batch query points must be [..., q, {engine.d}], got {a.shape}")
+    lead, q = a.shape[:-2], a.shape[-2]
+    if not 2 <= q <= BATCH_EI_MAX_Q:
+        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
+    G = int(np.prod(lead)) if lead else 1
+    p1, p2, S = _sobol_args(a, q, w1, w2)
+    out, po = GPEngine._out(a, lead)
+    engine._chk(engine._lib.tgp_batch_ei(engine._h, a.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), po, a.where))
+    return out
+
+
+def batch_ei_moments(engine, mean, cov, w1, w2, eta: float):
+    """The same tail on caller-supplied moments: mean [..., q], cov [..., q, q] as a model's ``predict_joint`` returns them
+    -> [...] (tgp_batch_ei_moments == the reference's ``_compute_batch_expected_improvement`` behind the 1e-6 and the
+    change of sign of ``__call__``).  Needs no data on the engine."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei_moments"):
+        return engine.batch_ei_moments(mean, cov, w1, w2, eta)
+    m, c = _Arg(mean), _Arg(cov)
+    if len(m.shape) < 1 or c.shape != m.shape + (m.shape[-1],):
+        raise ValueError(f"mean must be [..., q] and cov [..., q, q], got {m.shape} and {c.shape}")
+    if m.where != c.where:
+        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    lead, q = m.shape[:-1], m.shape[-1]
+    if not 2 <= q <= BATCH_EI_MAX_Q:
+        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
+    G = int(np.prod(lead)) if lead else 1
+    p1, p2, S = _sobol_args(m, q, w1, w2)
+    out, po = GPEngine._out(m, lead)
+    engine._chk(engine._lib.tgp_batch_ei_moments(engine._h, m.ptr, c.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), po, m.where))
+    return out
