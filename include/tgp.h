@@ -267,13 +267,29 @@ int tgp_qei(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps,
  * 1e-6 I inside every CDF's factorisation (utils.py:114, 143-144), 1e-12 on the factor's diagonal, the quantile's argument
  * kept in [1e-6, 1 - 1e-6] (utils.py:177).  The value is NOT clipped at zero.  2 <= q <= 16 (q = 1 is an error in the
  * reference as well: MultivariateNormalCDF(dim = 0)), S >= 1, else TGP_ERR_SHAPE / TGP_ERR_ARG; TGP_ERR_NOT_PD names the
- * first group one of whose factorisations met a non-positive pivot.  Value only: no gradient behind this entry yet.
+ * first group one of whose factorisations met a non-positive pivot.  Value only; the gradient is behind
+ * tgp_batch_ei_value_grad below.
  *   tgp_batch_ei_moments: the same tail on caller-supplied moments, mean [G,q] and cov [G,q,q] AS THE MODEL RETURNS THEM
  *     (the entry applies the 1e-6 and the change of sign itself); needs no data on the handle. */
 int tgp_batch_ei(tgp_handle h, const double* Xq, int64_t G, int q, const double* w1, const double* w2, int S,
                  double eta, double* out, int where);
 int tgp_batch_ei_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* w1,
                          const double* w2, int S, double eta, double* out, int where);
+
+/* The same function with its gradient, for the L-BFGS-B refinement of a q-batch (the reference differentiates it by TF
+ * autodiff through predict_joint, the Cholesky factors and Phi^-1).  Same constants, same limits (2 <= q <= 16, S >= 1),
+ * same errors as the two entries above; float64, fixed summation orders, no atomics: identical calls return identical bits.
+ *   tgp_batch_ei_moments_grad: the tail alone on caller-supplied moments (needs no data on the handle): val [G] = what
+ *     tgp_batch_ei_moments returns, gmean [G,q] = d val / d mean, gcov [G,q,q] SYMMETRIC with d val = sum_ij gcov_ij dcov_ij
+ *     for every symmetric dcov (the formula reads one triangle of cov in places, so the derivative by a single entry is not
+ *     defined; the symmetric adjoint is, and it is what tgp_joint_vjp takes).
+ *   tgp_batch_ei_value_grad: Xq [G,q,d] -> val [G], grad [G,q,d] = d val / d Xq: tgp_joint_forward's arrays, the tail with
+ *     its moment adjoints and tgp_joint_vjp's second half on the same K*^T and W K*, one synchronisation.  G * q <= 2048 else
+ *     TGP_ERR_SHAPE.  A diagonal entry of the covariance that the posterior clipped at 1e-12 gets zero adjoint. */
+int tgp_batch_ei_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                              const double* w2, int S, double eta, double* val, double* gmean, double* gcov, int where);
+int tgp_batch_ei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, const double* w1, const double* w2, int S,
+                            double eta, double* val, double* grad, int where);
 
 /* == BatchReparametrizationSampler.sample (sampler.py:208-287) itself: out [G,S,q] = mean +
  * (chol(cov + jitter*I) eps)^T for Xq [G,q,d], eps [q,S].  q <= 64. */

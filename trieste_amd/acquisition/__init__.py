@@ -9,7 +9,8 @@ from .function import (AugmentedExpectedImprovement, BatchExpectedImprovement, B
                        ExpectedImprovement,
                        MonteCarloExpectedImprovement, NegativeLowerConfidenceBound, ProbabilityOfImprovement,
                        augmented_expected_improvement, batch_expected_improvement,
-                       batch_monte_carlo_expected_improvement, expected_improvement,
+                       batch_monte_carlo_expected_improvement, differentiable_batch_expected_improvement,
+                       expected_improvement,
                        monte_carlo_expected_improvement, negative_lower_confidence_bound,
                        probability_below_threshold)
 from .greedy_batch import (Fantasizer, LocalPenalization, PenalizedAcquisition, hard_local_penalizer,

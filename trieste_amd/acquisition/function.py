@@ -388,7 +388,8 @@ class batch_expected_improvement(AcquisitionFunctionClass):
     """The analytic multi-point expected improvement of Chevalier and Ginsbourger, its multivariate normal CDFs estimated
     with Genz's sequential conditioning on fixed Sobol points (function.py:1281-1805, function/utils.py:29-199).  Posterior
     and tail run on the device (``trieste_amd.engine.batch_ei``); 2 <= q <= 16 points per batch; value only (no
-    ``value_and_gradient`` yet: ``batchify_joint`` optimizes it by random search).
+    ``value_and_gradient``: ``batchify_joint`` optimizes it by random search; the subclass
+    :class:`differentiable_batch_expected_improvement` adds the gradient).
 
     ``jitter`` is kept and, as in the reference, never applied: ``__call__`` adds a hard-coded 1e-6 to the covariance
     (function.py:1776-1783) and every CDF another 1e-6 (utils.py:114).
@@ -435,22 +436,53 @@ class batch_expected_improvement(AcquisitionFunctionClass):
         return batch_ei(self._engine, x, w1, w2, self._eta)[..., None]
 
 
-class BatchExpectedImprovement(SingleModelAcquisitionBuilder):
-    """Builder for the analytic batch EI (function.py:1189-1278); eta = min posterior mean at the observed points."""
+class differentiable_batch_expected_improvement(batch_expected_improvement):
+    """:class:`batch_expected_improvement` with its gradient w.r.t. the batch: what TF autodiff takes through
+    ``predict_joint``, the Cholesky factors and ``Phi^-1`` when the reference hands the function to
+    ``batchify_joint(generate_continuous_optimizer)``, here in one device call per chunk
+    (``trieste_amd.engine.batch_ei_value_grad``: joint posterior, the tail with its moment adjoints, the posterior's
+    vector-Jacobian product).  Having ``value_and_gradient`` is what routes it to the continuous optimizer."""
 
-    def __init__(self, sample_size: int, *, jitter: float = JITTER):
+    def value_and_gradient(self, points):
+        """points [P, q, D] -> (values [P], gradients [P, q, D])."""
+        from ..engine import BATCH_EI_MAX_Q, batch_ei_value_grad
+
+        x = np.ascontiguousarray(points.cpu().numpy() if _is_torch(points) else points, dtype=np.float64)
+        if x.ndim != 3:
+            raise ValueError(f"points must be [P, q, D], got shape {x.shape}")
+        P, q, _ = x.shape
+        if not 2 <= q <= BATCH_EI_MAX_Q:
+            raise ValueError(f"BatchExpectedImprovement takes batches of 2 to {BATCH_EI_MAX_Q} points, got {q}")
+        w1, w2 = self.sobol(q)
+        values, grads = np.empty(P), np.empty(x.shape)
+        chunk = max(1, getattr(self._engine, "JOINT_SMALL_POINTS", 2048) // q)
+        for g0 in range(0, P, chunk):
+            v, g = batch_ei_value_grad(self._engine, x[g0:g0 + chunk], w1, w2, self._eta)
+            values[g0:g0 + chunk], grads[g0:g0 + chunk] = np.asarray(v), np.asarray(g)
+        return values, grads
+
+
+class BatchExpectedImprovement(SingleModelAcquisitionBuilder):
+    """Builder for the analytic batch EI (function.py:1189-1278); eta = min posterior mean at the observed points.
+    ``differentiable=True`` builds the function with ``value_and_gradient`` (L-BFGS-B over the whole batch instead of a
+    random search over batches); the default leaves the function value-only."""
+
+    def __init__(self, sample_size: int, *, jitter: float = JITTER, differentiable: bool = False):
         if sample_size <= 0:
             raise ValueError(f"sample_size must be positive, got {sample_size}")
         if jitter < 0:
             raise ValueError(f"jitter must be non-negative, got {jitter}")
         self._sample_size = sample_size
         self._jitter = jitter
+        self._differentiable = bool(differentiable)
 
     def __repr__(self) -> str:
-        return f"BatchExpectedImprovement({self._sample_size!r}, jitter={self._jitter!r})"
+        extra = ", differentiable=True" if self._differentiable else ""
+        return f"BatchExpectedImprovement({self._sample_size!r}, jitter={self._jitter!r}{extra})"
 
     def prepare_acquisition_function(self, model, dataset: Optional[Dataset] = None):
-        return batch_expected_improvement(self._sample_size, model, _eta_from(model, dataset), self._jitter)
+        cls = differentiable_batch_expected_improvement if self._differentiable else batch_expected_improvement
+        return cls(self._sample_size, model, _eta_from(model, dataset), self._jitter)
 
     def update_acquisition_function(self, function, model, dataset: Optional[Dataset] = None):
         if not isinstance(function, batch_expected_improvement):

@@ -2632,6 +2632,110 @@ int tgp_batch_ei_moments(tgp_handle h, const double* mean, const double* cov, in
   return bei_finish(h);
 }
 
+// ---- the analytic batch EI's gradient: bei_grad_tail_kernel on given moments, and tgp_qei_value_grad's body around it ---------------
+int tgp_batch_ei_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                              const double* w2, int S, double eta, double* val, double* gmean, double* gcov, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = bei_check(h, q, w1, w2, S)) return rc;
+  if (G < 0 || (G > 0 && (!mean || !cov || !val || !gmean || !gcov))) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (G == 0) return TGP_OK;
+  if (int rc = set_device(h)) return rc;
+  const double *dw1, *dw2, *dmean, *dcov;
+  if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
+  HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)q * q * 8));
+  double total_ms = 0.0;
+  int launches = 0;
+  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
+    const int64_t gc = std::min(chunk, G - g0);
+    // host residency: one staging buffer for the inputs (mean, cov), one for the outputs (val, gmean, gcov)
+    double *dval, *dgm, *dgc;
+    if (where == TGP_DEVICE) {
+      dmean = mean + g0 * q;
+      dcov = cov + g0 * q * q;
+      dval = val + g0;
+      dgm = gmean + g0 * q;
+      dgc = gcov + g0 * q * q;
+    } else {
+      HIPCHK(h, h->s_out1.reserve((size_t)gc * (q + q * q) * sizeof(double)));
+      HIPCHK(h, h->s_out2.reserve((size_t)gc * (1 + q + q * q) * sizeof(double)));
+      double* const in = h->s_out1.as<double>();
+      HIPCHK(h, hipMemcpyAsync(in, mean + g0 * q, (size_t)gc * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(in + gc * q, cov + g0 * q * q, (size_t)gc * q * q * sizeof(double), hipMemcpyHostToDevice,
+                               h->stream));
+      dmean = in;
+      dcov = in + gc * q;
+      dval = h->s_out2.as<double>();
+      dgm = dval + gc;
+      dgc = dgm + gc * q;
+    }
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // the events bracket the tail itself
+    launch_bei_grad_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, 0, dval, dgm, dgc, h->d_info.as<int>());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    if (where != TGP_DEVICE) {
+      HIPCHK(h, hipMemcpyAsync(val + g0, dval, (size_t)gc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(gmean + g0 * q, dgm, (size_t)gc * q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(gcov + g0 * q * q, dgc, (size_t)gc * q * q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (int rc = sync(h)) return rc;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;
+    ++launches;
+  }
+  h->last_ms = total_ms;
+  h->last_launches = launches;
+  return bei_finish(h);
+}
+
+// K*^T, W K*, Gram product, pick, the tail with its moment adjoints, mix, the A product, joint_vjp_tail: one synchronisation.
+int tgp_batch_ei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, const double* w1, const double* w2, int S,
+                            double eta, double* val, double* grad, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = bei_check(h, q, w1, w2, S)) return rc;
+  if (!val || !grad) return fail(h, TGP_ERR_ARG, "val / grad is NULL");
+  const double* dXq;
+  int64_t P, Ppad;
+  if (int rc = joint_small_common(h, Xq, G, q, where, &dXq, &P, &Ppad)) return rc;
+  const int64_t Npad = h->Npad;
+  const double *dw1, *dw2;
+  double *dval, *dgrad;
+  if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)P * h->d, where, &dgrad)) return rc;
+  const size_t part_doubles = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, h->dp));
+  HIPCHK(h, h->s_grad.reserve(((size_t)4 * Npad * Ppad + (size_t)Ppad * Ppad + part_doubles + (size_t)2 * P * (1 + q)) * sizeof(double)));
+  double* B = h->s_grad.as<double>();
+  double* C1 = B + (size_t)Npad * Ppad;
+  double* T1 = C1 + (size_t)Npad * Ppad;   // C1^T, then D
+  double* Z = T1 + (size_t)Npad * Ppad;
+  double* Spp = Z + (size_t)Npad * Ppad;
+  double* part = Spp + (size_t)Ppad * Ppad;
+  double* dmean = part + part_doubles;
+  double* dcov = dmean + P;
+  double* dgm = dcov + (size_t)P * q;
+  double* dgc = dgm + P;
+  const ModelDev m = model_dev(h);
+  HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  launch_kstar_t(h->stream, m, dXq, P, Ppad, B);
+  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B, Ppad, 0.0, C1, Ppad, 3))
+    return rc;
+  launch_transpose(h->stream, C1, Npad, Ppad, Ppad, T1, Npad);
+  if (int rc = gemm_tall(h, false, (int)Ppad, (int)Ppad, (int)Npad, 1.0, T1, Npad, C1, Ppad, 0.0, Spp, Ppad, 0)) return rc;
+  launch_predict_small_tail(h->stream, m, P, Ppad, B, C1, part, dmean, nullptr);
+  launch_joint_pick(h->stream, m, dXq, P, Ppad, q, Spp, dcov);
+  launch_bei_grad_tail(h->stream, dmean, dcov, G, q, dw1, dw2, S, eta, 1, dval, dgm, dgc, h->d_info.as<int>());
+  launch_joint_mix(h->stream, C1, dgc, P, Ppad, Npad, q, T1);
+  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_A.as<double>(), Npad, T1, Ppad, 0.0, Z, Ppad, 5))
+    return rc;
+  launch_joint_vjp_tail(h->stream, m, dXq, P, Ppad, q, B, C1, Z, part, dgm, dgc, dgrad);
+  if (int rc = stage_out_finish(h, dval, val, (size_t)G, where)) return rc;
+  if (int rc = stage_out_finish(h, dgrad, grad, (size_t)P * h->d, where)) return rc;
+  if (int rc = sync(h)) return rc;
+  return bei_finish(h);
+}
+
 int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S,
                         double jitter, double* out, int where) {
   if (!h) return TGP_ERR_ARG;

@@ -163,6 +163,11 @@ void launch_qei_grad_tail(hipStream_t s, const double* mean, const double* cov, 
 constexpr int BEI_MAX_Q = 16;
 void launch_bei_tail(hipStream_t s, const double* mean, const double* cov, int64_t G, int q, const double* w1,
                      const double* w2, int S, double eta, double* out, int* info);
+// the same value with its adjoints w.r.t. (mean, cov): gmean [G][q], gcov [G][q][q] symmetric (bei_grad_tail_kernel)
+size_t bei_grad_tail_lds_bytes(int q);
+void launch_bei_grad_tail(hipStream_t s, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                          const double* w2, int S, double eta, int zero_clipped, double* val, double* gmean, double* gcov,
+                          int* info);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

@@ -222,4 +222,366 @@ void launch_bei_tail(hipStream_t s, const double* mean, const double* cov, int64
   else launch_bei_tail_qp<BEI_MAX_Q>(s, mean, cov, G, q, w1, w2, S, eta, out, info);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The value AND its adjoints w.r.t. (mean, cov): the forward tail above, problem for problem and operation for operation
+// (same build, factorisation, chain, sums), and behind every problem its reverse pass, all inside the wave that owns it:
+//   chain     per sample, steps n-1 .. 0: e_r's adjoint = (prefix product)(suffix product) + ybar_r (1 - 2e-6) w_r / phi(y_r)
+//             [(Phi^-1)' = 1 / phi(y)], t_r's = ebar_r phi(t_r), through t_r = (x_r - sum_c C_rc y_c) / (C_rr + 1e-12) to xbar_r,
+//             Cbar_rc, Cbar_rr and ybar_c.  Prefix products, not f / e_r: an e_r may underflow to zero.
+//   sums      xbar [n] and Cbar [n (n + 1) / 2] over the samples.  QP <= 8: per-lane accumulators (the lane's samples in order),
+//             one butterfly per entry and problem.  QP = 16: 136 + 16 accumulators (304 registers) next to the chain's 80 doubles of
+//             state do not fit the register file, so every entry is reduced over the wave per 64-sample chunk and lane 0 adds the chunks in order.
+//   factor    Abar = C^-T sym(Phi(C^T Cbar)) C^-1, the in-wave form of qei_grad_tail_kernel (lane c owns column c / row c).
+//   problem   back through R^(i,k) = Sigma_uv - Sigma_ku Sigma_kv / Sigma_kk, c^(i,k) = d_u - d_k Sigma_ku / Sigma_kk and the
+//             weight Sigma_ki N(d_k; 0, Sigma_kk) (or mu_i - T) to the adjoints of Sigma^(i) [q][q] and d^(i) [q], and from
+//             there (rows by lane, row and column sums) into THIS WAVE's accumulators of cov's and mu's adjoints.
+// A wave meets its problems in index order and the four waves' accumulators are added in wave order by one thread per entry:
+// no floating-point atomics, the same bits from every call.  Every matrix adjoint is taken of the formula as written (which reads
+// cov as a full matrix); the output is its symmetric part -- the adjoint for symmetric perturbations, which is what
+// tgp_joint_vjp takes.  zero_clipped: a diagonal entry of cov at the posterior's floor (VAR_FLOOR) gets zero (the clip's adjoint).
+template <int QP>
+__global__ __launch_bounds__(64 * BEI_WAVES) void bei_grad_tail_kernel(const double* __restrict__ mean,
+                                                                       const double* __restrict__ cov, int64_t G, int q,
+                                                                       const double* __restrict__ w1,
+                                                                       const double* __restrict__ w2, int S, double eta,
+                                                                       int zero_clipped, double* __restrict__ val,
+                                                                       double* __restrict__ gmean, double* __restrict__ gcov,
+                                                                       int* __restrict__ info) {
+  extern __shared__ double bei_lds[];
+  constexpr bool IN_REGS = QP <= 8;
+  constexpr int NACC = IN_REGS ? QP * (QP + 1) / 2 : 1;
+  constexpr int NXACC = IN_REGS ? QP : 1;
+  const int64_t g = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ldq = q | 1;
+  const int nprob = q + q * q;
+  const int per_wave = 3 * q * ldq + 6 * q + q * q + q;
+  double* const cv = bei_lds;            // [q][q]: cov + 1e-6 I
+  double* const mu = cv + q * q;         // [q]: -mean
+  double* const term = mu + q;           // [q + q^2]
+  double* const Ls = term + nprob + wave * per_wave;   // the factor C [n][ldq]
+  double* const Ms = Ls + q * ldq;       // [n][ldq]: Cbar (lower) -> Abar (symmetric)
+  double* const Sb = Ms + q * ldq;       // [q][ldq]: the adjoint of Sigma^(i) of an inner problem
+  double* const xs = Sb + q * ldq;       // [q] the limits
+  double* const dg = xs + q;             // [q] C_rr + 1e-12
+  double* const ig = dg + q;             // [q] its inverse
+  double* const xb = ig + q;             // [q] the limits' adjoint
+  double* const db = xb + q;             // [q] the adjoint of d^(i) of an inner problem
+  double* const rho = db + q;            // [q] Sigma_ku / Sigma_kk of the kept indices
+  double* const cvb = rho + q;           // [q][q]: this wave's sum of cov's adjoint
+  double* const mub = cvb + q * q;       // [q]: of mu's
+  for (int t = threadIdx.x; t < q * q; t += 64 * BEI_WAVES)
+    cv[t] = cov[g * q * q + t] + (t / q == t % q ? 1e-6 : 0.0);
+  if ((int)threadIdx.x < q) mu[threadIdx.x] = -mean[g * q + threadIdx.x];
+  for (int t = lane; t < q * q + q; t += 64) cvb[t] = 0.0;   // (cvb and mub are contiguous)
+  __syncthreads();
+  const double T = -eta;
+  auto bcast = [](double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+  };
+  auto sig = [&](int i, int j, int k) {
+    const double a = (j != i && k != i) ? cv[j * q + k] : 0.0;
+    const double b = j != i ? cv[j * q + i] : 0.0;
+    const double c = k != i ? cv[i * q + k] : 0.0;
+    return ((a - b) - c) + cv[i * q + i];
+  };
+  auto dif = [&](int i, int j) {
+    const double b = j == i ? -T : 0.0;
+    const double m = (mu[j] - mu[i]) - (j == i ? mu[i] : 0.0);
+    return b - m;
+  };
+  auto wfence = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); };
+  for (int pr = wave; pr < nprob; pr += BEI_WAVES) {  // (wave-uniform)
+    const bool outer = pr < q;
+    const int i = outer ? pr : (pr - q) / q;
+    const int k = outer ? -1 : (pr - q) % q;
+    const int n = outer ? q : q - 1;
+    const bool live = lane < n;
+    const int u = lane + ((!outer && lane >= k) ? 1 : 0);   // this lane's index in 0..q-1 (live lanes)
+    double* const Lrow = Ls + (live ? lane : 0) * ldq;
+    double* const Mrow = Ms + (live ? lane : 0) * ldq;
+    if (live) {
+      if (outer) {
+        for (int c = 0; c < n; ++c) Lrow[c] = sig(i, u, c) + (c == lane ? 1e-6 : 0.0);
+        xs[lane] = dif(i, u);
+      } else {
+        const double skk = sig(i, k, k), sku = sig(i, k, u);
+        for (int c = 0; c < n; ++c) {
+          const int v = c + (c >= k ? 1 : 0);
+          Lrow[c] = (sig(i, u, v) - sku * sig(i, k, v) / skk) + (c == lane ? 1e-6 : 0.0);
+        }
+        xs[lane] = dif(i, u) - dif(i, k) * (sku / skk);
+        rho[lane] = sku / skk;
+      }
+      for (int c = 0; c < n; ++c) Mrow[c] = 0.0;
+      xb[lane] = 0.0;
+    }
+    for (int j = 0; j < n; ++j) {  // the factorisation of bei_tail_kernel
+      const double x = Lrow[j];
+      double dj = bcast(x, j);
+      if (!(dj > 0.0)) {
+        if (lane == 0) atomicCAS(info, 0, (int)(g % 2000000000) + 1);
+        dj = 1.0;
+      }
+      const double sd = sqrt(dj);
+      const double lij = lane == j ? sd : x / sd;
+      const bool below = live && lane > j;
+      if (live && lane >= j) Lrow[j] = lij;
+      const double nl = -lij;
+      for (int c = j + 1; c < n; ++c) {
+        const double lcj = bcast(lij, c);
+        if (below) Lrow[c] = fma(nl, lcj, Lrow[c]);
+      }
+      if (lane == j) {
+        dg[j] = sd + 1e-12;
+        ig[j] = 1.0 / (sd + 1e-12);
+      }
+    }
+    wfence();
+    auto over = [&](double t, int j) {
+      const double z = t * ig[j];
+      return fma(fma(-z, dg[j], t), ig[j], z);
+    };
+    const double t0 = over(xs[0], 0);
+    const double e0 = normal_cdf(t0);
+    double res;
+    if (n == 1) {
+      res = e0;
+      if (lane == 0) {
+        const double xr = normal_pdf(t0) * ig[0];
+        xb[0] = xr;
+        Ms[0] = -xr * t0;
+      }
+    } else {
+      const double* __restrict__ const w = outer ? w1 : w2;  // [S][n]
+      double acc = 0.0;
+      double Cb[NACC], Xb[NXACC];
+#pragma unroll
+      for (int a = 0; a < NACC; ++a) Cb[a] = 0.0;
+#pragma unroll
+      for (int a = 0; a < NXACC; ++a) Xb[a] = 0.0;
+      for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        const bool valid = s < S;
+        const double* const ws = w + (int64_t)(valid ? s : 0) * n;
+        double y[QP], tt[QP], ee[QP], pf[QP], yb[QP];
+        double e = e0, f = e0;
+        tt[0] = t0;
+        ee[0] = e0;
+        pf[0] = 1.0;
+#pragma unroll
+        for (int r = 1; r < QP; ++r) {
+          yb[r - 1] = 0.0;
+          if (r < n) {  // (wave-uniform)
+            y[r - 1] = normal_quantile_mid(1e-6 + (1.0 - 2e-6) * ws[r - 1] * e);
+            const double* const Lr = Ls + r * ldq;
+            double sum = 0.0;
+#pragma unroll
+            for (int c = 0; c < r; ++c) sum = fma(Lr[c], y[c], sum);
+            pf[r] = f;
+            tt[r] = over(xs[r] - sum, r);
+            e = normal_cdf(tt[r]);
+            ee[r] = e;
+            f = e * f;
+          }
+        }
+        if (valid) acc += f;
+        const double on = valid ? 1.0 : 0.0;
+        double sf = on;   // the product of the e's behind step r (zero on a lane without a sample)
+#pragma unroll
+        for (int r = QP - 1; r >= 0; --r) {
+          if (r < n) {  // (wave-uniform)
+            double eb = pf[r] * sf;
+            if (r < n - 1) eb = fma(yb[r], (1.0 - 2e-6) * ws[r] / normal_pdf(y[r]), eb);
+            const double xr = eb * normal_pdf(tt[r]) * ig[r];   // the adjoint of x_r (and minus that of the row's sum)
+            const double* const Lr = Ls + r * ldq;
+            if constexpr (IN_REGS) {
+              Xb[r] += xr;
+              Cb[r * (r + 1) / 2 + r] = fma(-xr, tt[r], Cb[r * (r + 1) / 2 + r]);
+#pragma unroll
+              for (int c = 0; c < r; ++c) Cb[r * (r + 1) / 2 + c] = fma(-xr, y[c], Cb[r * (r + 1) / 2 + c]);
+            } else {
+              const double sx = wave_sum(xr), sd_ = wave_sum(-xr * tt[r]);
+              if (lane == 0) {
+                xb[r] += sx;
+                Ms[r * ldq + r] += sd_;
+              }
+#pragma unroll
+              for (int c = 0; c < r; ++c) {
+                const double sc = wave_sum(-xr * y[c]);
+                if (lane == 0) Ms[r * ldq + c] += sc;
+              }
+            }
+#pragma unroll
+            for (int c = 0; c < r; ++c) yb[c] = fma(-xr, Lr[c], yb[c]);
+            sf *= ee[r];
+          }
+        }
+      }
+      res = wave_sum(acc) / (double)S;
+      if constexpr (IN_REGS) {
+#pragma unroll
+        for (int r = 0; r < QP; ++r) {
+          if (r < n) {
+            const double sx = wave_sum(Xb[r]);
+            if (lane == 0) xb[r] = sx;
+#pragma unroll
+            for (int c = 0; c <= r; ++c) {
+              const double sc = wave_sum(Cb[r * (r + 1) / 2 + c]);
+              if (lane == 0) Ms[r * ldq + c] = sc;
+            }
+          }
+        }
+      }
+    }
+    // the weight of this problem in the sum, the term, and the weight's adjoint pieces
+    double wgt, pdf = 0.0, skk = 1.0, dk = 0.0, ski = 0.0;
+    if (outer) {
+      wgt = mu[i] - T;
+    } else {
+      skk = sig(i, k, k);
+      dk = dif(i, k);
+      ski = sig(i, k, i);
+      const double sc = sqrt(skk), z = dk / sc;
+      pdf = 0.3989422804014327 * exp(-0.5 * z * z) / sc;
+      wgt = ski * pdf;
+    }
+    if (lane == 0) term[pr] = outer ? (mu[i] - T) * res : ski * pdf * res;
+    wfence();
+    const double scale = n == 1 ? wgt : wgt / (double)S;
+    if (live) {
+      for (int c = 0; c <= lane; ++c) Mrow[c] *= scale;
+      xb[lane] *= scale;
+    }
+    wfence();
+    // the factor's adjoint, lane = column: Q = tril(C^T Cbar) / 2 in place, mirrored, C^-T from the left, C^-1 from the right
+    if (live)
+      for (int a = lane; a < n; ++a) {
+        double t = 0.0;
+        for (int c = a; c < n; ++c) t = fma(Ls[c * ldq + a], Ms[c * ldq + lane], t);
+        Ms[a * ldq + lane] = 0.5 * t;
+      }
+    wfence();
+    if (live)
+      for (int a = 0; a < lane; ++a) Ms[a * ldq + lane] = Ms[lane * ldq + a];
+    wfence();
+    if (live)
+      for (int a = n - 1; a >= 0; --a) {
+        double t = Ms[a * ldq + lane];
+        for (int c = a + 1; c < n; ++c) t = fma(-Ls[c * ldq + a], Ms[c * ldq + lane], t);
+        Ms[a * ldq + lane] = t / Ls[a * ldq + a];
+      }
+    wfence();
+    if (live)
+      for (int a = n - 1; a >= 0; --a) {
+        double t = Mrow[a];
+        for (int c = a + 1; c < n; ++c) t = fma(-Ls[c * ldq + a], Mrow[c], t);
+        Mrow[a] = t / Ls[a * ldq + a];
+      }
+    wfence();
+    // back through the problem's construction to the adjoints of Sigma^(i) (Sp) and d^(i) (dp)
+    const double* Sp = Ms;
+    const double* dp = xb;
+    double mu_i_extra = 0.0;   // what the weight adds to mu_i's adjoint
+    if (outer) {
+      mu_i_extra = res;
+    } else {
+      // lane b: h_b = sum_a Abar_ba rho_a; row u(b) of Sp = row b of Abar spread over the kept columns, column k zero
+      double hb = 0.0, kk = 0.0, dkb = 0.0;
+      if (live) {
+        for (int a = 0; a < n; ++a) hb = fma(Mrow[a], rho[a], hb);
+        double* const Srow = Sb + u * ldq;
+        for (int a = 0; a < n; ++a) Srow[a + (a >= k ? 1 : 0)] = Mrow[a];
+        Srow[k] = 0.0;
+        const double xbl = xb[lane];
+        Sb[k * ldq + u] = -2.0 * hb - xbl * dk / skk;
+        kk = (hb + xbl * dk / skk) * rho[lane];
+        dkb = -xbl * rho[lane];
+        db[u] = xbl;
+      }
+      kk = wave_sum(kk);
+      dkb = wave_sum(dkb);
+      const double z2 = dk * dk / skk;
+      const double pdfbar = res * ski;   // the weight is Sigma_ki pdf: its adjoint is res
+      if (lane == 0) {
+        Sb[k * ldq + k] = kk + pdfbar * pdf * (z2 - 1.0) / (2.0 * skk);
+        db[k] = dkb - pdfbar * pdf * dk / skk;
+      }
+      wfence();
+      if (lane == 0) Sb[k * ldq + i] += res * pdf;
+      wfence();
+      Sp = Sb;
+      dp = db;
+    }
+    {  // Sigma^(i)_jk = [j != i][k != i] cv_jk - [j != i] cv_ji - [k != i] cv_ik + cv_ii;  d_j = mu_i - mu_j (+ delta_ij (mu_i - T))
+      double rs = 0.0, cs = 0.0, dj = 0.0;
+      if (lane < q) {
+        for (int c = 0; c < q; ++c) {
+          rs += Sp[lane * ldq + c];
+          cs += Sp[c * ldq + lane];
+        }
+        dj = dp[lane];
+        if (lane != i) {
+          for (int c = 0; c < q; ++c)
+            if (c != i) cvb[lane * q + c] += Sp[lane * ldq + c];
+          cvb[lane * q + i] -= rs;
+          cvb[i * q + lane] -= cs;
+          mub[lane] -= dj;
+        }
+      }
+      const double tot = wave_sum(rs), dtot = wave_sum(dj);
+      if (lane == i) {
+        cvb[i * q + i] += tot;
+        mub[i] += dtot + mu_i_extra;
+      }
+    }
+    wfence();  // the next problem overwrites this wave's rows
+  }
+  __syncthreads();
+  const int stride = per_wave;
+  const double* const cvb0 = term + nprob + 3 * q * ldq + 6 * q;   // wave 0's accumulators
+  for (int t = threadIdx.x; t < q * q; t += 64 * BEI_WAVES) {
+    const int r = t / q, c = t % q;
+    double a = 0.0;
+    for (int wv = 0; wv < BEI_WAVES; ++wv) a += cvb0[wv * stride + r * q + c] + cvb0[wv * stride + c * q + r];
+    a *= 0.5;
+    if (zero_clipped && r == c && !(cov[g * q * q + t] > VAR_FLOOR)) a = 0.0;
+    gcov[g * q * q + t] = a;
+  }
+  if ((int)threadIdx.x < q) {
+    double a = 0.0;
+    for (int wv = 0; wv < BEI_WAVES; ++wv) a += cvb0[wv * stride + q * q + threadIdx.x];
+    gmean[g * q + threadIdx.x] = -a;
+  }
+  if (threadIdx.x == 0) {
+    double v = 0.0;
+    for (int i = 0; i < q; ++i) {
+      double inner = 0.0;
+      for (int k = 0; k < q; ++k) inner += term[q + i * q + k];
+      v += term[i] + inner;
+    }
+    val[g] = v;
+  }
+}
+
+size_t bei_grad_tail_lds_bytes(int q) {
+  return (size_t)(q * q + q + q + q * q + BEI_WAVES * (3 * q * (q | 1) + 6 * q + q * q + q)) * sizeof(double);
+}
+template <int QP>
+static void launch_bei_grad_tail_qp(hipStream_t s, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                                    const double* w2, int S, double eta, int zero_clipped, double* val, double* gmean,
+                                    double* gcov, int* info) {
+  hipLaunchKernelGGL(bei_grad_tail_kernel<QP>, dim3((unsigned)G), dim3(64 * BEI_WAVES), bei_grad_tail_lds_bytes(q), s, mean, cov,
+                     G, q, w1, w2, S, eta, zero_clipped, val, gmean, gcov, info);
+}
+void launch_bei_grad_tail(hipStream_t s, const double* mean, const double* cov, int64_t G, int q, const double* w1,
+                          const double* w2, int S, double eta, int zero_clipped, double* val, double* gmean, double* gcov,
+                          int* info) {
+  if (q <= 4) launch_bei_grad_tail_qp<4>(s, mean, cov, G, q, w1, w2, S, eta, zero_clipped, val, gmean, gcov, info);
+  else if (q <= 8) launch_bei_grad_tail_qp<8>(s, mean, cov, G, q, w1, w2, S, eta, zero_clipped, val, gmean, gcov, info);
+  else launch_bei_grad_tail_qp<BEI_MAX_Q>(s, mean, cov, G, q, w1, w2, S, eta, zero_clipped, val, gmean, gcov, info);
+}
+
 }  // namespace tgp

@@ -738,3 +738,43 @@ def batch_ei_moments(engine, mean, cov, w1, w2, eta: float):
     out, po = GPEngine._out(m, lead)
     engine._chk(engine._lib.tgp_batch_ei_moments(engine._h, m.ptr, c.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), po, m.where))
     return out
+
+
+def batch_ei_moments_grad(engine, mean, cov, w1, w2, eta: float):
+    """The tail with its adjoints on caller-supplied moments: mean [G, q], cov [G, q, q] -> (value [G], gmean [G, q],
+    gcov [G, q, q]) with gcov symmetric, d value = sum gcov * dcov for every symmetric dcov (tgp_batch_ei_moments_grad).
+    Needs no data on the engine."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei_moments_grad"):
+        return engine.batch_ei_moments_grad(mean, cov, w1, w2, eta)
+    m, c = _Arg(mean), _Arg(cov)
+    if len(m.shape) != 2 or c.shape != m.shape + (m.shape[-1],):
+        raise ValueError(f"mean must be [G, q] and cov [G, q, q], got {m.shape} and {c.shape}")
+    if m.where != c.where:
+        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    G, q = m.shape
+    if not 2 <= q <= BATCH_EI_MAX_Q:
+        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
+    p1, p2, S = _sobol_args(m, q, w1, w2)
+    val, pv = GPEngine._out(m, (G,))
+    gm, pgm = GPEngine._out(m, (G, q))
+    gc, pgc = GPEngine._out(m, (G, q, q))
+    engine._chk(engine._lib.tgp_batch_ei_moments_grad(engine._h, m.ptr, c.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), pv, pgm,
+                                                      pgc, m.where))
+    return val, gm, gc
+
+
+def batch_ei_value_grad(engine, Xq, w1, w2, eta: float):
+    """Xq [G, q, d] (2 <= q <= 16, G * q <= 2048) -> (analytic batch EI [G], its gradient [G, q, d]) in one device call:
+    the joint posterior, the tail with its moment adjoints and the posterior's vector-Jacobian product
+    (tgp_batch_ei_value_grad)."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei_value_grad"):
+        return engine.batch_ei_value_grad(Xq, w1, w2, eta)
+    a, G, q = engine._joint_small(Xq)
+    if not 2 <= q <= BATCH_EI_MAX_Q:
+        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
+    p1, p2, S = _sobol_args(a, q, w1, w2)
+    val, pv = GPEngine._out(a, (G,))
+    grad, pg = GPEngine._out(a, (G, q, engine.d))
+    if G:
+        engine._chk(engine._lib.tgp_batch_ei_value_grad(engine._h, a.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), pv, pg, a.where))
+    return val, grad
