@@ -1,8 +1,13 @@
 """torch float64 autograd restatement of ``tests/batch_ei_reference.py::batch_ei_parts``: the yardstick of the analytic
 batch EI's gradient.  Same formulas, same constants, same reference lines (function.py:1315-1805, utils.py:109-199), written
-on torch tensors (``torch.linalg.cholesky``, ``torch.special.ndtr`` / ``ndtri``) so that autograd differentiates through
+on torch tensors (``torch.linalg.cholesky``, ``torch.special.erfc`` / ``ndtri``) so that autograd differentiates through
 the factors and the quantile the way TF autodiff does in the reference -- independent of the hand-derived adjoint of the
 device kernel.  Test infrastructure, CPU only, never imported by the package.
+
+Phi is 0.5 erfc(-z / sqrt 2), not ``torch.special.ndtr``: torch's float64 ``ndtr`` is 0.5 (1 + erf(z / sqrt 2)), which
+loses the lower tail (0.0 at z = -10, 2 % off at z = -8) where the ``erfc`` form agrees with scipy's ``ndtr`` to the last
+digits.  With ``ndtr`` the value of a batch whose threshold lies 12 posterior standard deviations below its smallest mean
+was off by two orders of magnitude and the gradient by up to all of its largest entry.
 """
 from __future__ import annotations
 
@@ -11,6 +16,12 @@ import torch
 
 CALL_JITTER = 1e-6
 CDF_JITTER = 1e-6
+_SQRT_HALF = 0.7071067811865476
+
+
+def _ndtr(z):
+    """Phi(z), accurate in the lower tail and differentiable by autograd."""
+    return 0.5 * torch.special.erfc(-_SQRT_HALF * z)
 
 
 def _mvn_cdf(x, cov, w):
@@ -18,14 +29,14 @@ def _mvn_cdf(x, cov, w):
     P, n = x.shape
     C = torch.linalg.cholesky(cov + CDF_JITTER * torch.eye(n, dtype=x.dtype)[None])
     S = w.shape[0]
-    e = torch.special.ndtr(x[:, None, 0] / (C[:, None, 0, 0] + 1e-12)).expand(P, max(S, 1))
+    e = _ndtr(x[:, None, 0] / (C[:, None, 0, 0] + 1e-12)).expand(P, max(S, 1))
     f = e
     ys = []
     for i in range(1, n):
         ys.append(torch.special.ndtri(1e-6 + (1 - 2e-6) * w[None, :, i - 1] * e))
         y = torch.stack(ys, dim=-1)                                           # [P, S, i]
         tot = torch.sum(C[:, None, i, :i] * y, dim=-1)
-        e = torch.special.ndtr((x[:, None, i] - tot) / (C[:, None, i, i] + 1e-12))
+        e = _ndtr((x[:, None, i] - tot) / (C[:, None, i, i] + 1e-12))
         f = e * f
     return torch.mean(f, dim=-1)
 
