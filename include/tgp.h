@@ -340,7 +340,14 @@ int tgp_sample_joint(tgp_handle h, const double* Xq, int64_t n, const double* ep
  * (sampler.py:661-738) given the draws: rff_W [F,d], rff_b [F] (the RFF basis, gpflux
  * RandomFourierFeaturesCosine), w [F,B] (prior weights), xi [N,B] (noise draws).
  * v = (K + noise I)^-1 ((Y - c) + sqrt(noise) xi - Phi_Z w) is computed from the CACHED factor
- * (the reference re-factorises per trajectory, sampler.py:730).  All inputs HOST. */
+ * (the reference re-factorises per trajectory, sampler.py:730).  All inputs HOST.
+ *
+ * A trajectory BELONGS TO THE FACTORISATION IT WAS DRAWN FROM (both kinds): its weights are solved for -- and sized by --
+ * the N, inputs and hyper-parameters of the handle at creation, and its kernels read the handle's model.  Once that model
+ * is gone or replaced -- tgp_set_hyper, tgp_set_data, tgp_append_data, tgp_nlml_trial, tgp_clone_from INTO the handle, a
+ * failed update -- every call below on the older trajectory (tgp_traj_eval, _value_grad, _argmin, _argmin_async, _get_v,
+ * _get_theta; tgp_group_traj_argmin through its members) returns TGP_ERR_STATE and touches nothing: draw a new one (only
+ * tgp_traj_destroy remains).  tgp_nlml_trial_batch leaves the posterior untouched, so trajectories live across it. */
 int tgp_traj_create(tgp_handle h, const double* rff_W, const double* rff_b, int F, const double* w,
                     const double* xi, int B, tgp_traj* out);
 /* == RandomFourierFeatureTrajectorySampler._prepare_weight_sampler + theta_posterior.sample(B)

@@ -12,9 +12,25 @@ import numpy as np
 from oracle import gp_oracle as O
 
 
+def _stamp(traj, eng):
+    """A trajectory belongs to the factorisation it was drawn from (tgp_traj_s: the handle's data_version and N)."""
+    traj._state, traj._version, traj.N = eng._st(), eng._version, eng.N
+
+
+def _live(traj):
+    """What every tgp_traj_* entry checks first: TGP_ERR_STATE (RuntimeError) once the model has moved on."""
+    eng = traj._eng
+    if eng.state is None:
+        raise RuntimeError("stale trajectory: the model has no posterior: draw a new one")
+    if eng._version != traj._version:
+        raise RuntimeError("stale trajectory: the model was refactorised since the trajectory was drawn: draw a new one")
+    return traj._state
+
+
 class FakeTrajectory:
     def __init__(self, eng, W, b, w, xi):
         self._eng = eng
+        _stamp(self, eng)
         self.W, self.b = np.asarray(W, float), np.asarray(b, float)
         self.w = np.asarray(w, float).reshape(self.W.shape[0], -1)
         self.F, self.B = self.W.shape[0], self.w.shape[1]
@@ -24,13 +40,14 @@ class FakeTrajectory:
         pass
 
     def v(self):
+        _live(self)
         return self._v
 
     def __call__(self, Xq):
-        return O.trajectory_eval(self._eng.state, self.W, self.b, self.w, self._v, np.asarray(Xq, float))
+        return O.trajectory_eval(_live(self), self.W, self.b, self.w, self._v, np.asarray(Xq, float))
 
     def value_and_gradient(self, Xq):
-        return O.trajectory_value_and_grad(self._eng.state, self.W, self.b, self.w, self._v, np.asarray(Xq, float))
+        return O.trajectory_value_and_grad(_live(self), self.W, self.b, self.w, self._v, np.asarray(Xq, float))
 
     def argmin(self, Xq, index_base=0):
         vals = self(np.asarray(Xq, float))
@@ -51,6 +68,7 @@ def _pairs(vals, idx):
 class FakeRffTrajectory:
     def __init__(self, eng, W, b, eps):
         self._eng = eng
+        _stamp(self, eng)
         self.W, self.b = np.asarray(W, float), np.asarray(b, float)
         self._theta = O.rff_theta(eng.state, self.W, self.b, np.asarray(eps, float))
         self.F, self.B = self._theta.shape
@@ -59,20 +77,21 @@ class FakeRffTrajectory:
         pass
 
     def theta(self):
+        _live(self)
         return self._theta
 
     def argmin_pairs(self, Xq, index_base=0):
         return _pairs(*self.argmin(Xq, index_base))
 
     def __call__(self, Xq):
-        return O.rff_trajectory_eval(self._eng.state, self.W, self.b, self._theta, np.asarray(Xq, float))
+        return O.rff_trajectory_eval(_live(self), self.W, self.b, self._theta, np.asarray(Xq, float))
 
     def value_and_gradient(self, Xq):
         Xq = np.asarray(Xq, float)
-        zero_v = np.zeros((self._eng.N, self.B))
-        scale = np.sqrt(2.0 * self._eng.state.variance / self.F)
+        st = _live(self)
+        zero_v = np.zeros((self.N, self.B))
         # the decoupled oracle with no canonical part: w = theta (its features carry the scale themselves)
-        return O.trajectory_value_and_grad(self._eng.state, self.W, self.b, self._theta, zero_v, Xq)
+        return O.trajectory_value_and_grad(st, self.W, self.b, self._theta, zero_v, Xq)
 
     def argmin(self, Xq, index_base=0):
         vals = self(np.asarray(Xq, float))
@@ -93,6 +112,7 @@ class FakeEngine:
         self.d, self.kernel, self.device, self.N = int(d), kernel, device, 0
         self._hyper = None
         self.state = None
+        self._version = 0  # tgp_handle_s::data_version: moves with every factorisation and every clone into the handle
         self._pen = None
         self._ent = None
         self._rep = None
@@ -151,6 +171,7 @@ class FakeEngine:
         if other.d != self.d or other.kernel != self.kernel:
             raise ValueError("clone needs equal input dimension and kernel")
         self._hyper, self.state, self.N = other._hyper, other.state, other.N
+        self._version += 1
         FakeEngine.cloned += 1
 
     def clone(self):
@@ -252,6 +273,7 @@ class FakeEngine:
             self.state = None
             raise NotPositiveDefiniteError(str(e))
         self.N = X.shape[0]
+        self._version += 1
 
     def append_data(self, Xnew, Ynew):
         st = self._st()
@@ -286,6 +308,7 @@ class FakeEngine:
 
             raise NotPositiveDefiniteError(str(e))
         self.state, self.N = None, 0
+        self._version += 1
         return O.nlml_and_grad(st)[0]
 
     def update_is_persistent(self, N):

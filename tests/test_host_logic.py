@@ -541,6 +541,52 @@ def test_trajectory_fixed_batch_size_and_resample():
     np.testing.assert_allclose(vals.mean(1), model2.predict(xs)[0][:, 0], atol=0.5)
 
 
+def test_a_trajectory_belongs_to_the_model_it_was_drawn_from():
+    """include/tgp.h (trajectories): after the model is refactorised every tgp_traj_* call on an older trajectory is
+    refused with TGP_ERR_STATE.  The samplers always redraw (update_trajectory / resample_trajectory make a new engine
+    trajectory), so they keep working across a model update; an engine trajectory HELD across it raises."""
+    from trieste_amd.sampler import RandomFourierFeatureTrajectorySampler
+
+    rng = np.random.default_rng(4)
+    x = rng.uniform(size=(15, 2, 2))
+    for make in (lambda m: m.trajectory_sampler(), lambda m: RandomFourierFeatureTrajectorySampler(m, 40, seed=2)):
+        model, data = _model(n=14, noise=1e-2)
+        sampler = make(model)
+        traj = sampler.get_trajectory()
+        y0 = traj(x)
+        held = traj._traj  # the engine trajectory behind the sampler's object
+        extra = Dataset(rng.uniform(size=(3, 2)), rng.standard_normal((3, 1)))
+        model.update(data + extra)  # more rows (the append path): the held trajectory's weights are for N = 14
+        for call in (lambda: held(x), lambda: held.value_and_gradient(x), lambda: held.argmin(x[:, 0, :]),
+                     lambda: held.argmin_pairs(x[:, 0, :]), lambda: traj(x)):
+            with pytest.raises(RuntimeError, match="stale trajectory"):
+                call()
+        with pytest.raises(RuntimeError, match="stale trajectory"):
+            held.theta() if hasattr(held, "theta") else held.v()
+        sampler.update_trajectory(traj)
+        y1 = traj(x)
+        assert y1.shape == y0.shape and np.all(np.isfinite(y1)) and traj._traj is not held and traj._traj.N == 17
+        held = traj._traj
+        model.update(data)  # fewer rows (the full path)
+        with pytest.raises(RuntimeError, match="stale trajectory"):
+            held(x)
+        sampler.resample_trajectory(traj)
+        val, grad = traj.value_and_gradient(x)
+        assert val.shape == (15, 2) and grad.shape == (15, 2, 2) and traj._traj.N == 14
+        # a trial evaluation leaves no posterior, a clone into the engine replaces it: both refuse as well
+        held, eng = traj._traj, model.engine
+        other = eng.clone()
+        eng.clone_from(other)
+        with pytest.raises(RuntimeError, match="stale trajectory"):
+            held(x)
+        sampler.resample_trajectory(traj)
+        eng.nlml_trial_batch(np.array([[1.0, 0.3, 0.3, 1e-2, 0.0]]))  # promises an untouched posterior
+        np.testing.assert_array_equal(traj(x), traj(x))
+        eng.nlml_trial()
+        with pytest.raises(RuntimeError, match="stale trajectory"):
+            traj(x)
+
+
 # ---- loops (reference tests/unit/test_ask_tell_optimization.py, test_bayesian_optimizer.py) ---------
 def test_ask_tell_reduces_scaled_branin():
     """BASELINE config C1 plumbing on the host logic: Ask-Tell + EGO(EI) + random-search sweep."""

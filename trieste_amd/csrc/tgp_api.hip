@@ -1331,7 +1331,9 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
   if (info != 0)
     return fail(h, TGP_ERR_NOT_PD, "Cholesky failed: K + noise*I is not positive definite (pivot %d)",
                 info - 1);
-  h->have_data = !factor_only;  // (a factor-only trial leaves no posterior behind)
+  // a trial leaves no posterior behind (include/tgp.h), whether it built the factor only or -- below the persistent kernel's
+  // sizes -- went through a full update: what a query may rely on does not depend on the size or the launch policy
+  h->have_data = trial_value == nullptr;
   h->data_version = ++g_data_version;
   return TGP_OK;
 }
@@ -1471,6 +1473,7 @@ int tgp_nlml_trial_batch(tgp_handle h, const double* hypers, int B, double* valu
     const double v0 = h->variance, n0 = h->noise, c0 = h->mean_const;
     const std::vector<double> ls0 = h->ls;
     const bool had = h->have_data;
+    const uint64_t version0 = h->data_version;
     int rc_all = TGP_OK;
     for (int b = 0; b < B && rc_all == TGP_OK; ++b) {
       const double* hb = hypers + (size_t)b * (d + 3);
@@ -1482,7 +1485,10 @@ int tgp_nlml_trial_batch(tgp_handle h, const double* hypers, int B, double* valu
     }
     if (int rc = tgp_set_hyper(h, v0, ls0.data(), n0, c0)) return rc;
     if (rc_all != TGP_OK) return rc_all;
-    if (had) return factorise(h, h->N, 0);  // the handle's own posterior, as it was
+    if (had) {  // the handle's own posterior, as it was: the update is deterministic, so the factor comes back bit for bit
+      if (int rc = factorise(h, h->N, 0)) return rc;  // and keeps its stamp -- live trajectories and cached planes stay valid
+      h->data_version = version0;
+    }
     return TGP_OK;
   };
   if (!dag_applies(h, Npad) || Npad != h->Npad) return one_by_one();
@@ -1692,7 +1698,7 @@ int tgp_clone_from(tgp_handle dst, tgp_handle src) {
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(to.p, from.p, bytes, hipMemcpyDeviceToDevice, s);
   };
-  HIPCHK(dst, copy(dst->d_ls, src->d_ls, (size_t)src->d * sizeof(double)));
+  HIPCHK(dst, copy(dst->d_ls, src->d_ls, (size_t)src->dp * sizeof(double)));  // (with the padding entries, as tgp_set_hyper)
   if (src->have_data) {
     // every entry point of the source synchronises its stream before returning: its state is complete
     const size_t N = (size_t)src->N, Npad = (size_t)src->Npad, nn = Npad * Npad * sizeof(double);
@@ -1706,6 +1712,10 @@ int tgp_clone_from(tgp_handle dst, tgp_handle src) {
     HIPCHK(dst, copy(dst->d_W, src->d_W, nn));
     HIPCHK(dst, copy(dst->d_alpha, src->d_alpha, Npad * sizeof(double)));
     HIPCHK(dst, copy(dst->d_err, src->d_err, Npad * sizeof(double)));
+    // the work vectors every factorisation sizes for itself: tgp_traj_create solves through them at the CLONED Npad, and the
+    // target may never have factorised, or only a smaller model
+    HIPCHK(dst, dst->d_tmp1.reserve(Npad * sizeof(double)));
+    HIPCHK(dst, dst->d_tmp2.reserve(Npad * sizeof(double)));
     dst->N = src->N;
     dst->Npad = src->Npad;
     dst->zeroed_L = src->zeroed_L == src->d_L.p ? dst->d_L.p : nullptr;  // the copies carry the zeros along
@@ -2785,6 +2795,19 @@ static TrajDev traj_dev(tgp_traj t) {
   return td;
 }
 
+// A trajectory belongs to the factorisation it was built from: its kernels walk the handle's CURRENT N, scaled inputs and
+// lengthscales against weights sized and solved for the model at creation.  TGP_OK, or the refusal (TGP_ERR_STATE).
+static int traj_live(tgp_traj t) {
+  tgp_handle h = t->h;
+  if (!h->have_data)
+    return fail(h, TGP_ERR_STATE, "stale trajectory: the model has no posterior (hyper-parameters or data changed since the "
+                "trajectory was drawn, or an update failed): draw a new one");
+  if (t->version != h->data_version)
+    return fail(h, TGP_ERR_STATE, "stale trajectory: the model was refactorised since the trajectory was drawn (N = %lld then, "
+                "%lld now): draw a new one", (long long)t->N, (long long)h->N);
+  return TGP_OK;
+}
+
 int tgp_traj_create(tgp_handle h, const double* rff_W, const double* rff_b, int F, const double* w,
                     const double* xi, int B, tgp_traj* out) {
   if (!h || !out) return TGP_ERR_ARG;
@@ -2800,6 +2823,8 @@ int tgp_traj_create(tgp_handle h, const double* rff_W, const double* rff_b, int 
   t->device = h->device;
   t->F = F;
   t->B = B;
+  t->version = h->data_version;
+  t->N = h->N;
   const int d = h->d, dp = h->dp;
   const int64_t N = h->N, Npad = h->Npad;
   std::vector<double> Wp((size_t)F * dp, 0.0), ws((size_t)F * B);
@@ -2877,6 +2902,8 @@ int tgp_traj_create_rff(tgp_handle h, const double* rff_W, const double* rff_b, 
   t->device = h->device;
   t->F = F;
   t->B = B;
+  t->version = h->data_version;
+  t->N = h->N;
   t->canonical = 0;
   const int d = h->d, dp = h->dp;
   const int64_t N = h->N, Npad = h->Npad;
@@ -2985,6 +3012,7 @@ int tgp_traj_get_theta(tgp_traj t, double* theta) {
   if (!t || !theta) return TGP_ERR_ARG;
   tgp_handle h = t->h;
   if (t->canonical) return fail(h, TGP_ERR_STATE, "not an RFF-weight trajectory");
+  if (int rc = traj_live(t)) return rc;
   if (int rc = set_device(h)) return rc;
   HIPCHK(h, hipMemcpy(theta, t->d_theta.p, (size_t)t->F * t->B * sizeof(double), hipMemcpyDeviceToHost));
   return TGP_OK;
@@ -3008,14 +3036,16 @@ int tgp_traj_get_v(tgp_traj t, double* v) {
   if (!t || !v) return TGP_ERR_ARG;
   tgp_handle h = t->h;
   if (!t->canonical) return fail(h, TGP_ERR_STATE, "an RFF-weight trajectory has no canonical weights");
+  if (int rc = traj_live(t)) return rc;
   if (int rc = set_device(h)) return rc;
-  HIPCHK(h, hipMemcpy(v, t->d_v.p, (size_t)h->N * t->B * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(v, t->d_v.p, (size_t)t->N * t->B * sizeof(double), hipMemcpyDeviceToHost));
   return TGP_OK;
 }
 
 int tgp_traj_eval(tgp_traj t, const double* Xq, int64_t M, int per_traj_inputs, double* out, int where) {
   if (!t) return TGP_ERR_ARG;
   tgp_handle h = t->h;
+  if (int rc = traj_live(t)) return rc;
   if (M < 0 || (M > 0 && (!Xq || !out))) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (M == 0) return TGP_OK;
   if (!per_traj_inputs && t->B > 16)
@@ -3040,6 +3070,7 @@ int tgp_traj_eval(tgp_traj t, const double* Xq, int64_t M, int per_traj_inputs, 
 int tgp_traj_value_grad(tgp_traj t, const double* Xq, int64_t P, double* val, double* grad, int where) {
   if (!t) return TGP_ERR_ARG;
   tgp_handle h = t->h;
+  if (int rc = traj_live(t)) return rc;
   if (P < 0 || (P > 0 && (!Xq || !val || !grad))) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (P == 0) return TGP_OK;
   if (int rc = set_device(h)) return rc;
@@ -3078,6 +3109,7 @@ int tgp_traj_argmin(tgp_traj t, const double* Xq, int64_t M, int64_t index_base,
                     int64_t* best_idx, int where) {
   if (!t) return TGP_ERR_ARG;
   tgp_handle h = t->h;
+  if (int rc = traj_live(t)) return rc;
   if (M < 1 || !Xq) return fail(h, TGP_ERR_SHAPE, "arg-min needs M >= 1 candidates");
   if (t->B > 16) return fail(h, TGP_ERR_SHAPE, "supports B <= 16 trajectories per call, got %d", t->B);
   if (int rc = set_device(h)) return rc;
@@ -3098,6 +3130,7 @@ int tgp_traj_argmin(tgp_traj t, const double* Xq, int64_t M, int64_t index_base,
 int tgp_traj_argmin_async(tgp_traj t, const double* Xq_device, int64_t M, int64_t index_base, double* pairs_device) {
   if (!t) return TGP_ERR_ARG;
   tgp_handle h = t->h;
+  if (int rc = traj_live(t)) return rc;
   if (M < 1 || !Xq_device) return fail(h, TGP_ERR_SHAPE, "arg-min needs M >= 1 candidates");
   if (!pairs_device) return fail(h, TGP_ERR_ARG, "pairs_device is NULL");
   if (t->B > 16) return fail(h, TGP_ERR_SHAPE, "supports B <= 16 trajectories per call, got %d", t->B);

@@ -160,6 +160,10 @@ struct tgp_traj_s {
   DevBuf d_W, d_b, d_ws, d_v, d_theta;
   int canonical = 1;
   int device = 0;  // copied from the handle: destruction must not dereference `h` (it may be gone already)
+  // a trajectory belongs to the factorisation it was built from: the handle's data_version and N at creation (d_v holds
+  // that N); every tgp_traj_* entry refuses once the handle's stamp has moved on or its posterior is gone
+  uint64_t version = 0;
+  int64_t N = 0;
 };
 
 // ---- internal entry points shared between the translation units (not part of the C-ABI) -------------

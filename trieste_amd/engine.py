@@ -594,6 +594,7 @@ class Trajectory:
                                           xi.ctypes.data, B, C.byref(t))
         eng._chk(rc)
         self._t, self.F, self.B = t, F, B
+        self.N = eng.N  # the model it was drawn from: the library refuses the trajectory once that model is replaced
 
     def theta(self):
         """Feature weights [F, B] of an RFF-weight trajectory."""
@@ -620,7 +621,7 @@ class Trajectory:
 
     def v(self):
         self._live()
-        out = np.empty((self._eng.N, self.B))
+        out = np.empty((self.N, self.B))
         self._eng._chk(self._eng._lib.tgp_traj_get_v(self._t, out.ctypes.data))
         return out
 
