@@ -24,8 +24,9 @@ __device__ __forceinline__ v4d mfma_f64(double a, double b, v4d c) {
 // The libm-grade sqrt/exp hipcc inlines cost ~45 VALU instructions per K* entry, most of it
 // special-case handling (scaling, class tests, overflow selects) that cannot trigger here:
 // sqrt is only called on [1e-36, 1e300] and exp only on (-inf, 0].  These versions keep full
-// double accuracy (<= 2 ulp, checked against the oracle in tests/test_gpu_parity.py) at roughly
-// half the instructions.
+// double accuracy (<= 2 ulp: tests/test_gpu_kernel_resolution.py checks every path that forms k(x, X)
+// against mpmath at eps (A + B s), s the argument of the exponential, and tests/test_fast_math_restatement.py
+// restates them on the CPU -- DESIGN.md section 4.5) at roughly half the instructions.
 typedef const __attribute__((address_space(4))) double* cptr;  // read-only data, scalar-loadable
 __device__ __forceinline__ cptr as_const(const double* p) {
   return (cptr)(const __attribute__((address_space(1))) double*)(p);
@@ -46,8 +47,10 @@ __device__ __forceinline__ double fast_sqrt_pos(double x) {
 
 // sqrt(x) and 1/sqrt(x) together (x > 0, normal range): the coupled Goldschmidt pair g -> sqrt(x),
 // h -> 1 / (2 sqrt(x)) with ONE coupled iteration (the pivot chain of the 64-leaf is a serial dependency of its
-// wave).  v_rsq_f64 delivers ~2^-26; one Goldschmidt step squares that, the residual step on g brings sqrt(x) to
-// ~1 ulp, 1/sqrt(x) to ~2 ulp.
+// wave).  The instruction set guide gives v_rsq_f64 2^29 ulp, a seed error e <= 2^-23 (about 2^-25 measured on an MI355X
+// through traj_sqrt below); one Goldschmidt step leaves 3/2 e^2 on g and on h alike, up to 96 eps by the documented seed
+// and about 8 eps by the measured one.  The residual step on g squares that again: sqrt(x) to ~1 ulp.  1/sqrt(x) = 2 h
+// has no residual step and keeps the 3/2 e^2.
 __device__ __forceinline__ void sqrt_and_rsqrt_short(double x, double& g_out, double& rs_out) {
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
@@ -142,9 +145,9 @@ __device__ __forceinline__ double kernel_from_r2(double r2, double variance) {
 // section 4.5) and, since round 6, the generating steps of the int8 sweep (tgp_kernels_sweep_i8.inc) -------------------------
 // shape(q) = k / variance as a function of q = SCALE r^2, with SCALE folded into the distance's constants (Matern:
 // sqrt(SCALE) r is the argument of both the polynomial and the exponential, so the multiplication by sqrt(3) / sqrt(5)
-// disappears); the variance multiplies the finished sum once per candidate instead of every entry; sqrt with ONE
-// residual step (~1 ulp) and exp without the underflow clamp (v_ldexp_f64 flushes by itself; the argument is bounded by
-// the inputs).  Same accuracy class as kernel_from_r2 (1 - 2 ulp), nine instructions fewer per entry for Matern-5/2.
+// disappears); the variance multiplies the finished sum once per candidate instead of every entry; sqrt with NO
+// residual step (traj_sqrt below) and exp without the underflow clamp (v_ldexp_f64 flushes by itself; the argument is bounded by
+// the inputs).  The exponential is at 1 - 2 ulp as in kernel_from_r2; the sqrt is NOT (see traj_sqrt).  Nine instructions fewer per entry for Matern-5/2.
 template <int KIND>
 struct TrajShape {
   // q = SCALE r^2 with log2(e) folded in as well (round 5): u = sqrt(q) IS the base-2 exponent of the exponential,
@@ -155,7 +158,9 @@ struct TrajShape {
   static constexpr double SCALE = KIND == KIND_RBF ? 0.5 * L2E : C * L2E * L2E;
   static constexpr double FLOOR = 1e-36 * SCALE;  // gpflow: r = sqrt(max(r^2, 1e-36))
 };
-// sqrt(x), x > 0: v_rsq_f64 (2^-26) + ONE coupled Goldschmidt step = 2^-51 relative.  (Rounds 3 / 4 added a residual step
+// sqrt(x), x > 0: v_rsq_f64 + ONE coupled Goldschmidt step: a seed error e leaves 3/2 e^2.  The instruction set guide gives
+// v_rsq_f64 2^29 ulp (e = 2^-23): up to 1.5 * 2^-46 = 96 eps (8 eps measured on an MI355X at s = 680,
+// tests/test_gpu_kernel_resolution.py).  On exp(-s) that is a relative error of up to 97.5 eps s.  (Rounds 3 / 4 added a residual step
 // for the last ulp: two instructions of ~50 per kernel evaluation that a sum of 8192 terms compared at 1e-5 cannot see.)
 __device__ __forceinline__ double traj_sqrt(double x) {
   const double y = __builtin_amdgcn_rsq(x);

@@ -172,7 +172,8 @@ __device__ __forceinline__ void i8_glds16s_slab(const unsigned char* sbase_unifo
 #ifndef TGP_I8_SHORTK
 #define TGP_I8_SHORTK 1    // round 6: the generating steps evaluate the kernel function in the SHORT forms of the trajectory kernel
                            // (tgp_dev.hpp traj_shape: log2(e) and sqrt(c) folded into the distance scale, one coupled Goldschmidt
-                           // step for the square root, 2^t with an exact fractional part; 1 - 2 ulp) -- ~27 instead of ~34 float64
+                           // step for the square root, 2^t with an exact fractional part; the exponential at 1 - 2 ulp, the square
+                           // root as far as traj_sqrt's comment says) -- ~27 instead of ~34 float64
                            // instructions per Matern-5/2 entry.  Round 5 measured a (less accurate) short form at 0.35 %: generation
                            // was bound by its scalar-load / LDS round trips then, not by its instruction count.
 #endif
