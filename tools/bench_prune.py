@@ -1,0 +1,52 @@
+"""The pruned EI arg-max against the unpruned one on the headline shape (development aid; bench.py is the contract).
+
+Two thresholds with the engine calls of bench.py's step: the model's eta (blocks are given up: the gain, with the
+counters of one step) and eta = -1e6 (every EI is 0, nothing can be given up: what the pruned kernel's generate-first
+phase and its checkpoints cost when they buy nothing).  --variant 2048 runs the unpruned kernel for the comparison; on a
+tree without the pruned kernel the counters are left out (TGP_TREE=<checkout> imports the package of another checkout,
+e.g. the parent commit's, for the same-box comparison).
+    python tools/bench_prune.py [--variant 2048] [--steps 10] [--warmup 3] [--workload headline|c2]"""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.environ.get("TGP_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from trieste_amd import objectives as O
+from trieste_amd.distributed import all_gather_winners
+from trieste_amd import engine as E
+from trieste_amd.engine import GPEngine
+
+SHAPES = {"headline": ("ackley", 8, "matern52", 4096, 1 << 20, 1e-2), "c2": ("hartmann_6", 6, "rbf", 1024, 1_000_000, 1e-2)}
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--variant", type=int, default=0)
+ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--workload", default="headline", choices=sorted(SHAPES))
+args = ap.parse_args()
+obj, d, kernel, N, M, noise = SHAPES[args.workload]
+X, Y = O.synthetic_problem(getattr(O, obj), d, N)
+eng = GPEngine(d, kernel)
+eng.set_variant(args.variant)
+eng.use_torch_stream()
+eng.set_hyper(1.0, O.default_lengthscales(d), noise, float(Y.mean()))
+eng.set_data(X, Y)
+Xq = eng.sample_box(5678, 0, M, 0.0, 1.0)
+for label, eta in (("eta", eng.eta()), ("eta=-1e6", -1e6)):
+    def step():
+        v, i = all_gather_winners(eng, eng.acq_argmax_pair("ei", eta, Xq, index_base=0))
+        return float(v[0]), int(i[0])
+    for _ in range(1 + args.warmup):
+        best = step()
+    kms = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        best = step()
+        kms.append(eng.last_kernel_ms()[0])
+    torch.cuda.synchronize()
+    out = dict(workload=args.workload, variant=args.variant, threshold=label, ms_per_step=(time.perf_counter() - t0) / args.steps * 1e3,
+               kernel_ms_mean=float(np.mean(kms)), kernel_ms_min=float(np.min(kms)), kernel_ms_max=float(np.max(kms)),
+               best_value=best[0], best_index=best[1])
+    if hasattr(E, "prune_counters"):
+        out["blocks, given up, row blocks skipped"] = E.prune_counters(eng)
+    print(json.dumps(out), flush=True)

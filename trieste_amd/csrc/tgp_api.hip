@@ -30,6 +30,10 @@ hipError_t launch_sweep_dma_kind0(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_sweep_dma_kind1(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_sweep_dma_kind2(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_sweep_dma_kind3(hipStream_t, const SweepArgs&, int64_t);
+hipError_t launch_sweep_prune_kind0(hipStream_t, const SweepArgs&, int64_t);
+hipError_t launch_sweep_prune_kind1(hipStream_t, const SweepArgs&, int64_t);
+hipError_t launch_sweep_prune_kind2(hipStream_t, const SweepArgs&, int64_t);
+hipError_t launch_sweep_prune_kind3(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_joint_kind0(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_joint_kind1(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_joint_kind2(hipStream_t, const SweepArgs&, int64_t);
@@ -159,7 +163,7 @@ void apply_penalization(tgp_handle h, double* dvals, const double* dXq, int64_t 
 //   VARIANT_DAG_ONE_CHAIN (512): the persistent `update` kernel's chain as ONE workgroup (rounds 3 - 5) instead of round 6's two
 constexpr int VARIANT_NO_SPLIT = 1, VARIANT_FORCE_SPLIT = 2, VARIANT_JOINT_V1 = 4, VARIANT_REG_STAGING = 8, VARIANT_NO_DAG = 16,
               VARIANT_DAG_SMALL = 32, VARIANT_NO_REPAIR_PRODUCT = 64, VARIANT_STATIC_BLOCKS = 128, VARIANT_DAG_WHOLE_TILES = 256,
-              VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024;
+              VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024, VARIANT_NO_PRUNE = 2048;
 //   VARIANT_SWEEP_SMALL_PREDICT (1024): tgp_predict at <= 2048 points through a sweep launch (rounds 1 - 5) instead of the skinny product
 constexpr int64_t REPAIR_PCAP = 512;   // TGP_PREC_AUTO: lists up to this many candidates are recomputed as a product
 int gemm_tall(tgp_handle h, bool tb, int m, int n, int k, double alpha, const double* A, int64_t lda, const double* B,
@@ -597,12 +601,33 @@ hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
     hipError_t ea = h->s_kcache.reserve((size_t)wg * (size_t)a.m.Npad * SW_BN * sizeof(double));
     if (ea != hipSuccess) return ea;
     am.kcache = h->s_kcache.as<double>();
+    // only the winner is consumed and EI grows with the variance: candidate blocks whose EI bound cannot win are given up
+    // at a row-block boundary (PRUNE instantiation; the same winner bit for bit)
+    const bool prune = a.acq_kind == TGP_ACQ_EI && a.blk_val && !a.acq_out && !a.mean_out && !a.var_out &&
+                       !(h->variant & VARIANT_NO_PRUNE);
+    if (prune) {
+      ea = h->s_prune.reserve(3 * sizeof(unsigned long long));
+      if (ea != hipSuccess) return ea;
+      am.prune = h->s_prune.as<unsigned long long>();
+    }
     (void)hipEventRecord(h->ev0, h->stream);
-    switch (h->kind) {
-      case TGP_RBF: e = launch_sweep_dma_kind0(h->stream, a, wg); break;
-      case TGP_MATERN12: e = launch_sweep_dma_kind1(h->stream, a, wg); break;
-      case TGP_MATERN32: e = launch_sweep_dma_kind2(h->stream, a, wg); break;
-      default: e = launch_sweep_dma_kind3(h->stream, a, wg); break;
+    if (prune) {
+      e = hipMemsetAsync(am.prune, 0, 3 * sizeof(unsigned long long), h->stream);
+      if (e != hipSuccess) return e;
+      h->prune_blocks = grid;
+      switch (h->kind) {
+        case TGP_RBF: e = launch_sweep_prune_kind0(h->stream, a, wg); break;
+        case TGP_MATERN12: e = launch_sweep_prune_kind1(h->stream, a, wg); break;
+        case TGP_MATERN32: e = launch_sweep_prune_kind2(h->stream, a, wg); break;
+        default: e = launch_sweep_prune_kind3(h->stream, a, wg); break;
+      }
+    } else {
+      switch (h->kind) {
+        case TGP_RBF: e = launch_sweep_dma_kind0(h->stream, a, wg); break;
+        case TGP_MATERN12: e = launch_sweep_dma_kind1(h->stream, a, wg); break;
+        case TGP_MATERN32: e = launch_sweep_dma_kind2(h->stream, a, wg); break;
+        default: e = launch_sweep_dma_kind3(h->stream, a, wg); break;
+      }
     }
     (void)hipEventRecord(h->ev1, h->stream);
     h->last_launches = 1;
@@ -1027,7 +1052,7 @@ int tgp_destroy(tgp_handle h) {
   }
   for (DevBuf* b : {&h->d_xc, &h->d_xn, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
                     &h->d_err, &h->d_tmp1, &h->d_tmp2, &h->d_info, &h->d_pen, &h->d_ent, &h->d_repv, &h->d_wq, &h->d_rs, &h->d_xsa, &h->s_ent, &h->s_in, &h->s_in2, &h->s_out1,
-                    &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_xqw, &h->s_rep,
+                    &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_xqw, &h->s_rep, &h->s_prune,
                     &h->s_rep_stats, &h->d_dag_flags, &h->d_dag_trace})
     b->release();
 
@@ -2310,6 +2335,7 @@ static int enqueue_argmax(tgp_handle h, int acq_kind, double param, const double
                           double* dval, int64_t* didx) {
   h->last_launches = 0;
   h->last_ms = 0.0;
+  h->prune_blocks = 0;
   if ((h->pen_kind != 0 && h->pen_P > 0) || acq_kind >= TGP_ACQ_MES) {
     HIPCHK(h, h->s_out3.reserve((size_t)M * sizeof(double)));
     double* dvals = h->s_out3.as<double>();
@@ -3146,6 +3172,20 @@ int tgp_stream_synchronize(tgp_handle h) {
   if (int rc = set_device(h)) return rc;
   if (int rc = sync(h)) return rc;
   HIPCHK(h, hipGetLastError());
+  return TGP_OK;
+}
+
+int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int64_t* row_blocks_skipped) {
+  if (!h) return TGP_ERR_ARG;
+  unsigned long long w[3] = {0, 0, 0};
+  if (h->prune_blocks > 0) {
+    if (int rc = set_device(h)) return rc;
+    HIPCHK(h, hipMemcpyAsync(w, h->s_prune.p, sizeof w, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sync(h)) return rc;
+  }
+  if (blocks) *blocks = h->prune_blocks;
+  if (given_up) *given_up = (int64_t)w[1];
+  if (row_blocks_skipped) *row_blocks_skipped = (int64_t)w[2];
   return TGP_OK;
 }
 

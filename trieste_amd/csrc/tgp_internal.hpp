@@ -88,6 +88,10 @@ struct SweepArgs {
                           // repair pass over the flagged candidates is enqueued without a host round trip)
   double* xqw;            // wide sweeps (dp > MAX_D): [grid][dp][128] per-workgroup scaled candidate coordinates (device
                           // scratch beside the K* slabs; the narrow instantiations keep them in LDS)
+  // the pruned EI arg-max (PRUNE instantiation of sweep_dma_kernel): [0] the bits of the best finished block maximum
+  // (EI >= 0: unsigned order is value order), [1] candidate blocks given up, [2] row blocks they skipped; ALL ZERO at
+  // launch (memset before every launch: a stale best would be a wrong result)
+  unsigned long long* prune;
 };
 constexpr double I8_TIGHT = 1.0078125;  // digit-plane scales S_i = I8_TIGHT max_k |W_ik|, S' = I8_TIGHT variance: the
                                         // balanced digits reach |q| <= 0x7f7f7f7f = 0.99609 2^31 > 2^31 / I8_TIGHT

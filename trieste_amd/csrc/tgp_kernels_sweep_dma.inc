@@ -101,9 +101,19 @@ __device__ __forceinline__ void dma_kstep(v4d (&acc)[4][2], uint32_t la, uint32_
   }
 }
 
-template <int KIND, int DP>
+// PRUNE (tgp_kernels_sweep_prune_k*.hip, the EI arg-max alone): a candidate block is given up at a row-block boundary once
+// no candidate of it can still win.  The column norms only grow, so `variance - partial norm` bounds the variance from
+// above and EI, increasing in the variance, from above with it; the bound is compared with the launch's best finished
+// block maximum (SweepArgs::prune).  For that the block's K* is generated BEFORE the step loop (same thread -> entry
+// mapping and order as generate_B: the mean is bit-identical and known before the first MFMA) and every B tile comes
+// from the slab by DMA.  The instantiations without PRUNE compile to what they were.
+constexpr int D_PRUNE_LDS = 5 * DBN + 2;   // [4][128] checkpoint norms, [128] means, two vote words
+constexpr double PRUNE_MIN_BEST = 1e-280, PRUNE_MARGIN = 1.0 + 0x1p-14;
+
+template <int KIND, int DP, bool PRUNE>
 __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
-  __shared__ __attribute__((aligned(16))) double smem[3 * D_ASTAGE + 2 * D_BSTAGE + DBN * DP];
+  static_assert(!PRUNE || TGP_DMA_DEFER, "the checkpoint sits behind the deferred MFMAs");
+  __shared__ __attribute__((aligned(16))) double smem[3 * D_ASTAGE + 2 * D_BSTAGE + DBN * DP + (PRUNE ? D_PRUNE_LDS : 0)];
   double* const sAbase = smem;                       // three A stages
   double* const sBbase = smem + 3 * D_ASTAGE;        // two B stages
   double* const xqs = smem + 3 * D_ASTAGE + 2 * D_BSTAGE;  // [DP][128] scaled candidate coordinates
@@ -126,6 +136,10 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   double* const sred = smem + 1024;  // [4][128]
   double* const bvs = smem + 1536;
   int64_t* const bis = (int64_t*)(smem + 1540);
+  // PRUNE: areas of their own behind xqs (mred / sred alias A stage 0, which is in use at a checkpoint)
+  double* const psred = xqs + DBN * DP;         // [4][128]
+  double* const pmean = psred + 4 * DBN;        // [128]
+  int* const pvote = (int*)(pmean + DBN);       // [2]
 
   double* const kc = a.kcache + (size_t)blockIdx.x * (size_t)Npad * DBN;
   const int64_t nblk = (a.M + DBN - 1) / DBN;
@@ -145,6 +159,45 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
       for (int j = 0; j < 2; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
     double ssq0 = 0.0, ssq1 = 0.0, macc = 0.0;
     __syncthreads();  // xqs is read by other threads below; every DMA of the previous block has been waited for
+
+    if constexpr (PRUNE) {
+      // generate first: the whole K* of the block into the slab, the mean into pmean.  Entry for entry the arithmetic of
+      // generate_B, k-steps in the order the sweep meets them
+      double xr[DP];
+#pragma unroll
+      for (int c = 0; c < DP; ++c) xr[c] = xqs[c * DBN + kcol];
+      for (int g = 0; g < nb * DKSTEPS; ++g) {
+        const int64_t krow0 = (int64_t)g * DBK + 2 * krg;
+        const cptr xs = as_const(a.m.Xs + krow0 * DP);
+        const cptr al = as_const(a.m.alpha + krow0);
+        double r2[2] = {0.0, 0.0};
+#pragma unroll
+        for (int c = 0; c < DP; ++c) {
+#pragma unroll
+          for (int r = 0; r < 2; ++r) {
+            const double t0 = xr[c] - xs[r * DP + c];
+            r2[r] = fma(t0, t0, r2[r]);
+          }
+        }
+        double* kcp = kc + krow0 * DBN + kcol;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const double kv = kernel_from_r2<KIND>(r2[r], variance);
+          macc = fma(kv, al[r], macc);
+          kcp[r * DBN] = kv;
+        }
+      }
+      mred[krg * 128 + kcol] = macc;   // (no DMA is in flight: A stage 0 is free)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the slab stores, before the barrier that lets the DMA read them
+      __syncthreads();
+      if (tid < 128) {
+        double m = 0.0;
+#pragma unroll
+        for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
+        pmean[tid] = m + a.m.mean_const;
+      }
+      __syncthreads();   // mred is A stage 0 again
+    }
 
     // wave w moves row w of a tile: the two 1 KiB halves of the Wt row, the whole 1 KiB K* row
     auto dma_A = [&](int stage, int ib, int kb, int ks) {
@@ -216,13 +269,43 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
     };
+    // PRUNE checkpoint (all accumulators have just been folded and cleared): true when every candidate's EI bound lies
+    // below the best finished block maximum by more than the tail's own resolution -- one decision per workgroup
+    auto cannot_win = [&]() -> bool {
+      double s0 = ssq0, s1 = ssq1;
+      s0 += __shfl_xor(s0, 16, 64);
+      s0 += __shfl_xor(s0, 32, 64);
+      s1 += __shfl_xor(s1, 16, 64);
+      s1 += __shfl_xor(s1, 32, 64);
+      if (lane < 16) {
+        psred[wm * 128 + wn * 32 + lane] = s0;
+        psred[wm * 128 + wn * 32 + 16 + lane] = s1;
+      }
+      __syncthreads();
+      if (tid < 128) {
+        bool out = true;   // (columns past M have nothing to lose)
+        if (blk * DBN + tid < a.M) {
+          const double s = (psred[tid] + psred[128 + tid]) + (psred[256 + tid] + psred[384 + tid]);
+          const double ub = acq_tail(ACQ_EI, a.acq_param, pmean[tid], fmax(variance - s, VAR_FLOOR), a.m.noise);
+          const double best = __longlong_as_double(
+              (long long)__hip_atomic_load(a.prune, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+          out = best > PRUNE_MIN_BEST && ub * PRUNE_MARGIN < best;   // (a NaN bound compares false: never given up)
+        }
+        const int all_out = __all(out);
+        if (lane == 0) pvote[w] = all_out;
+      }
+      __syncthreads();
+      return __builtin_amdgcn_readfirstlane(pvote[0] & pvote[1]) != 0;
+    };
+    bool given_up = false;
     int ib = 0, kb = 0, ks = 0;        // tile t
     int ib1 = 0, kb1 = 0, ks1 = 0;     // tile t + 1
     advance(ib1, kb1, ks1);
     // prologue: Wt tiles 0 and 1 in flight, K* tile 0 generated (k-step (0, 0) is always a first use)
     dma_A(0, 0, 0, 0);
+    if constexpr (PRUNE) dma_B(0, 0, 0);
     if (T > 1) dma_A(1, ib1, kb1, ks1);
-    generate_B(0, 0, 0);
+    if constexpr (!PRUNE) generate_B(0, 0, 0);
     if (T > 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -244,7 +327,7 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
       int ib2 = ib1, kb2 = kb1, ks2 = ks1;  // tile t + 2
       advance(ib2, kb2, ks2);
       const bool has1 = t + 1 < T, has2 = t + 2 < T;
-      const bool gen1 = has1 && kb1 == ib1;  // tile t + 1 brings K* rows seen for the first time
+      const bool gen1 = !PRUNE && has1 && kb1 == ib1;  // tile t + 1 brings K* rows seen for the first time
       if (TGP_DMA_DEFER) {
         __builtin_amdgcn_s_setprio(2);
         flush_deferred();
@@ -252,6 +335,12 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
         if (pend_fold) {
           fold_block();
           pend_fold = false;
+          if constexpr (PRUNE) {
+            if (cannot_win()) {   // row blocks ib .. nb - 1 are not needed
+              given_up = true;
+              break;
+            }
+          }
         }
       }
       if (has1 && !gen1) dma_B((t + 1) & 1, kb1, ks1);
@@ -305,8 +394,21 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
       flush_deferred();
       if (pend_fold) fold_block();
     }
+    if constexpr (PRUNE) {
+      if (given_up) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the Wt DMA of the next tile is still in flight
+        if (tid == 0) {
+          a.blk_val[blk] = -INFINITY;   // as a block without a valid candidate
+          a.blk_idx[blk] = INT64_MAX;
+          atomicAdd(a.prune + 1, 1ull);
+          atomicAdd(a.prune + 2, (unsigned long long)(nb - ib));
+        }
+        __syncthreads();  // LDS is rewritten by the next block
+        continue;
+      }
+    }
     // ---- reductions (LDS is free after the last barrier; no DMA is outstanding) --------------------------
-    mred[krg * 128 + kcol] = macc;
+    if constexpr (!PRUNE) mred[krg * 128 + kcol] = macc;
     {
       double s0 = ssq0, s1 = ssq1;
       s0 += __shfl_xor(s0, 16, 64);
@@ -325,9 +427,11 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
       const int64_t cj = blk * DBN + tid;
       if (cj < a.M) {
         double m = 0.0;
+        if constexpr (!PRUNE) {
 #pragma unroll
-        for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
-        const double mean = m + a.m.mean_const;
+          for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
+        }
+        const double mean = PRUNE ? pmean[tid] : m + a.m.mean_const;
         const double s = (sred[tid] + sred[128 + tid]) + (sred[256 + tid] + sred[384 + tid]);
         const double var = fmax(variance - s, VAR_FLOOR);
         if (a.mean_out) a.mean_out[cj] = mean;
@@ -360,21 +464,24 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
         }
         a.blk_val[blk] = v0;
         a.blk_idx[blk] = i0;
+        if constexpr (PRUNE) {   // EI >= 0: the bit patterns order like the values (a -0.0 or a rounded-negative value stays out)
+          if (v0 > 0.0) atomicMax(a.prune, (unsigned long long)__double_as_longlong(v0));
+        }
       }
     }
     __syncthreads();  // scratch / xqs are rewritten by the next block
   }
 }
 
-template <int KIND>
+template <int KIND, bool PRUNE>
 hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) {
   dim3 g((unsigned)grid), b(1024);
   switch (a.m.dp) {
-    case 2: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 2>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 4>), g, b, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 6>), g, b, 0, s, a); break;
-    case 8: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 8>), g, b, 0, s, a); break;
-    case 16: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 16>), g, b, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 2, PRUNE>), g, b, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 4, PRUNE>), g, b, 0, s, a); break;
+    case 6: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 6, PRUNE>), g, b, 0, s, a); break;
+    case 8: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 8, PRUNE>), g, b, 0, s, a); break;
+    case 16: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 16, PRUNE>), g, b, 0, s, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -382,8 +489,19 @@ hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) 
 
 }  // namespace
 
-hipError_t TGP_CAT(launch_sweep_dma_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid) {
-  return launch_sweep_dma_dp<TGP_SWEEP_KIND>(s, a, grid);
+#ifndef TGP_CAT
+#define TGP_CAT2(a, b) a##b
+#define TGP_CAT(a, b) TGP_CAT2(a, b)
+#endif
+// one translation unit holds either the plain instantiations or the PRUNE ones (tgp_kernels_sweep_prune_k*.hip)
+#ifdef TGP_SWEEP_PRUNE_TU
+hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid) {
+  return launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
 }
+#else
+hipError_t TGP_CAT(launch_sweep_dma_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid) {
+  return launch_sweep_dma_dp<TGP_SWEEP_KIND, false>(s, a, grid);
+}
+#endif
 
 }  // namespace tgp

@@ -568,6 +568,15 @@ class GPEngine:
         return Trajectory(self, rff_W, rff_b, w, xi)
 
 
+def prune_counters(eng: "GPEngine"):
+    """(candidate blocks, blocks given up, row blocks skipped) of ``eng``'s most recent arg-max; zeros when it did not run
+    the pruned EI sweep (tgp_get_prune_counters).  A measurement aid beside the engine, not part of the surface the
+    acquisition code drives: synchronises the engine's stream."""
+    b, g, r = C.c_int64(), C.c_int64(), C.c_int64()
+    eng._chk(eng._lib.tgp_get_prune_counters(eng._h, C.byref(b), C.byref(g), C.byref(r)))
+    return b.value, g.value, r.value
+
+
 class Trajectory:
     """B decoupled trajectories sharing one RFF basis (tgp_traj_*)."""
 
