@@ -28,7 +28,8 @@
  *     afterwards is allowed (garbage collectors finalise in arbitrary order).
  *   - acquisition modifiers are handle state: tgp_set_penalization / tgp_set_min_value_samples /
  *     tgp_set_repulsion apply to every later tgp_acq_* call on that handle until cleared; none of them touches
- *     the model (data, hyper-parameters, factorisation).
+ *     the model (data, hyper-parameters, factorisation).  tgp_set_ehvi_partition is state of the same kind for the
+ *     tgp_ehvi_* calls that name the handle first.
  *   - no torch types, no C++ types: plain pointers and sizes only.
  */
 #ifndef TGP_H
@@ -290,6 +291,47 @@ int tgp_batch_ei_moments_grad(tgp_handle h, const double* mean, const double* co
                               const double* w2, int S, double eta, double* val, double* gmean, double* gcov, int where);
 int tgp_batch_ei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, const double* w1, const double* w2, int S,
                             double eta, double* val, double* grad, int where);
+
+/* ---- expected hypervolume improvement ---------------------------------------------------- */
+/* == expected_hv_improvement (acquisition/function/multi_objective.py:145-250) over a stack of P independent exact GPRs, one
+ * handle per objective (minimisation).  The cells of the non-dominated region have bounds lb, ub [K,P]; the reference's
+ * sum over the 2^P corners of (Psi(lb) - Psi(ub))^+ and nu is evaluated as
+ *     EHVI(x) = sum_cells prod_j max(g_j(ub_j) - g_j(lb_j), 0),  g_j(t) = E[(t - Y_j)^+] = s_j pdf(z) + (t - m_j) cdf(z),
+ *     z = (t - m_j) / s_j,  t = max(bound, -1e10) (the reference's clip; g is exactly 0 there),
+ * which is the same number (the nu terms cancel) and keeps the tails where the reference's 1 - cdf flushes to zero.  Every
+ * bound is one of a few distinct values per objective (anti-reference point, front points, reference point), so the
+ * partition is handed over as per-objective tables of distinct bounds and per-cell indices into them; the kernel tabulates g
+ * once per (candidate, objective, distinct bound) and streams the cells as index pairs.
+ * Limits: 2 <= P <= 4 objectives, 1 <= n_bounds[j] <= 512 distinct bounds per objective, 1 <= K <= 2^21 cells, else
+ * TGP_ERR_SHAPE.  float64; the summation order over the cells is a function of (P, max_j n_bounds[j], K) alone and there are
+ * no atomics: a candidate's value depends on its own moments and the partition only, and identical calls return identical bits.
+ *   tgp_set_ehvi_partition: handle state on the LEADING handle (hs[0] below), the counterpart of
+ *     expected_hv_improvement.update as tgp_set_min_value_samples is for the entropy tails.  bounds: host
+ *     [P, bounds_stride], row j ascending and distinct with n_bounds[j] valid entries, none of them +inf or NaN (-inf is
+ *     clipped like every bound below -1e10); lower_idx / upper_idx: host [K,P] int32 indices into those rows.  K == 0 clears
+ *     the state (the other arguments are then ignored).  An index out of range, lower above upper, a row that is not
+ *     ascending or bounds_stride below the largest count: TGP_ERR_ARG.
+ *   tgp_ehvi_moments: the tail alone on caller-supplied moments, mean and var [P,M] OBJECTIVE-MAJOR (host or device), var taken
+ *     as given (> 0 is the caller's duty); needs no data on the handle; out [M].  TGP_ERR_STATE without a partition.
+ *   tgp_ehvi_values: hs = P handles (one per objective: same device, same d, else TGP_ERR_ARG; P must equal the partition's;
+ *     a handle without data or a leading handle without partition: TGP_ERR_STATE; errors are reported on hs[0]); Xq [M,d]
+ *     is staged once; every handle's (mean, var clipped at 1e-12) comes from tgp_predict ITSELF on that handle (the
+ *     small-product path up to 2048 points, the sweep above, in whatever arithmetic the handle is set to), written
+ *     objective-major into scratch of the leading handle (16 P M bytes of device memory); out [M].  The handles may
+ *     use different streams (tgp_predict synchronises its own).
+ *   tgp_ehvi_argmax: the same followed by the arg-max over the values (one trip of 8 B per candidate through device memory, as
+ *     the penalised and entropy tails); conventions of tgp_acq_argmax: host outputs, the first index wins ties, M < 1 is
+ *     TGP_ERR_SHAPE.
+ *   tgp_ehvi_last_ms: of the most recent of the three calls above on this (leading) handle: the summed times of the P
+ *     posterior sweeps (what tgp_last_kernel_ms reports after tgp_ehvi_values / _argmax; 0 for the small-product path and for
+ *     tgp_ehvi_moments) and the time of the tail kernel. */
+int tgp_set_ehvi_partition(tgp_handle h, int P, const double* bounds, int bounds_stride, const int* n_bounds,
+                           const int32_t* lower_idx, const int32_t* upper_idx, int64_t K);
+int tgp_ehvi_moments(tgp_handle h, const double* mean, const double* var, int64_t M, double* out, int where);
+int tgp_ehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t M, double* out, int where);
+int tgp_ehvi_argmax(const tgp_handle* hs, int P, const double* Xq, int64_t M, int64_t index_base, double* best_val,
+                    int64_t* best_idx, double* best_x, int where);
+int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms);
 
 /* == BatchReparametrizationSampler.sample (sampler.py:208-287) itself: out [G,S,q] = mean +
  * (chol(cov + jitter*I) eps)^T for Xq [G,q,d], eps [q,S].  q <= 64. */

@@ -63,6 +63,11 @@ SIGNATURES = {
     "tgp_batch_ei_moments_grad": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp,
                                             C.c_int]),
     "tgp_batch_ei_value_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp, C.c_int]),
+    "tgp_set_ehvi_partition": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int64]),
+    "tgp_ehvi_moments": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int]),
+    "tgp_ehvi_values": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, C.c_int]),
+    "tgp_ehvi_argmax": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _dp, _ip, _vp, C.c_int]),
+    "tgp_ehvi_last_ms": (C.c_int, [_vp, _dp, _dp]),
     "tgp_reparam_samples": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int]),
     "tgp_traj_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_create_rff": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
@@ -149,6 +154,7 @@ MERGES = {"rccl": 0, "peer": 1}
 PRECISIONS = {"f64": 0, "i8x4": 1, "i8x5": 2, "auto": 3}
 MAX_D = 1024      # input dimensions tgp_create accepts (include/tgp.h)
 NARROW_MAX_D = 32  # above it: float64 sweeps only (no int8 rungs), no trajectories
+EHVI_MAX_P, EHVI_MAX_BOUNDS, EHVI_MAX_CELLS = 4, 512, 1 << 21  # limits of the tgp_ehvi_* calls (include/tgp.h)
 
 
 def check(lib, handle, rc, group=False):

@@ -18,6 +18,9 @@ from .greedy_batch import (Fantasizer, LocalPenalization, PenalizedAcquisition, 
 from .interface import (AcquisitionFunctionBuilder, AcquisitionFunctionClass, GreedyAcquisitionFunctionBuilder,
                         SingleModelAcquisitionBuilder, SingleModelGreedyAcquisitionBuilder,
                         SingleModelVectorizedAcquisitionBuilder, VectorizedAcquisitionFunctionBuilder)
+from .multi_objective import (DividedAndConquerNonDominated, ExactPartition2dNonDominated, ExpectedHypervolumeImprovement,
+                              Pareto, expected_hv_improvement, get_reference_point, non_dominated,
+                              prepare_default_non_dominated_partition_bounds)
 from .optimizer import (FailedOptimizationError, automatic_optimizer_selector, batchify_joint, batchify_vectorize,
                         generate_continuous_optimizer, generate_initial_points, generate_random_search_optimizer,
                         optimize_discrete, sample_from_space)

@@ -1051,7 +1051,7 @@ int tgp_destroy(tgp_handle h) {
     (void)hipStreamSynchronize(nullptr);
   }
   for (DevBuf* b : {&h->d_xc, &h->d_xn, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
-                    &h->d_err, &h->d_tmp1, &h->d_tmp2, &h->d_info, &h->d_pen, &h->d_ent, &h->d_repv, &h->d_wq, &h->d_rs, &h->d_xsa, &h->s_ent, &h->s_in, &h->s_in2, &h->s_out1,
+                    &h->d_err, &h->d_tmp1, &h->d_tmp2, &h->d_info, &h->d_pen, &h->d_ent, &h->d_ehvi, &h->s_ehvi, &h->d_repv, &h->d_wq, &h->d_rs, &h->d_xsa, &h->s_ent, &h->s_in, &h->s_in2, &h->s_out1,
                     &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_xqw, &h->s_rep, &h->s_prune,
                     &h->s_rep_stats, &h->d_dag_flags, &h->d_dag_trace})
     b->release();
@@ -3186,6 +3186,223 @@ int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int
   if (blocks) *blocks = h->prune_blocks;
   if (given_up) *given_up = (int64_t)w[1];
   if (row_blocks_skipped) *row_blocks_skipped = (int64_t)w[2];
+  return TGP_OK;
+}
+
+// ---- expected hypervolume improvement (tgp_kernels_ehvi.hip) ----------------------------------------------------
+int tgp_set_ehvi_partition(tgp_handle h, int P, const double* bounds, int bounds_stride, const int* n_bounds,
+                           const int32_t* lower_idx, const int32_t* upper_idx, int64_t K) {
+  if (!h) return TGP_ERR_ARG;
+  if (K == 0) {
+    h->ehvi_K = 0;
+    h->ehvi_P = 0;
+    return TGP_OK;
+  }
+  if (P < 2 || P > EHVI_MAX_P)
+    return fail(h, TGP_ERR_SHAPE, "expected hypervolume improvement takes 2..%d objectives, got %d", EHVI_MAX_P, P);
+  if (K < 0 || K > EHVI_MAX_CELLS)
+    return fail(h, TGP_ERR_SHAPE, "the partition must have 1..%lld cells, got %lld", (long long)EHVI_MAX_CELLS, (long long)K);
+  if (!bounds || !n_bounds || !lower_idx || !upper_idx) return fail(h, TGP_ERR_ARG, "bad arguments");
+  int V = 0;
+  for (int j = 0; j < P; ++j) {
+    if (n_bounds[j] < 1 || n_bounds[j] > EHVI_MAX_BOUNDS)
+      return fail(h, TGP_ERR_SHAPE, "objective %d has %d distinct bounds: 1..%d are supported", j, n_bounds[j], EHVI_MAX_BOUNDS);
+    V = std::max(V, n_bounds[j]);
+  }
+  if (bounds_stride < V) return fail(h, TGP_ERR_ARG, "bounds_stride %d is below the largest bound count %d", bounds_stride, V);
+  std::vector<double> hb((size_t)P * V, 0.0);
+  for (int j = 0; j < P; ++j)
+    for (int v = 0; v < n_bounds[j]; ++v) {
+      const double b = bounds[(size_t)j * bounds_stride + v];
+      if (!(b < INFINITY) || (v > 0 && !(b > bounds[(size_t)j * bounds_stride + v - 1])))
+        return fail(h, TGP_ERR_ARG, "the bounds of objective %d must be ascending, distinct and below +inf (entry %d)", j, v);
+      hb[(size_t)j * V + v] = b;
+    }
+  std::vector<uint32_t> hc((size_t)K * P);
+  for (int64_t k = 0; k < K; ++k)
+    for (int j = 0; j < P; ++j) {
+      const int32_t lo = lower_idx[k * P + j], hi = upper_idx[k * P + j];
+      if (lo < 0 || hi < 0 || lo >= n_bounds[j] || hi >= n_bounds[j])
+        return fail(h, TGP_ERR_ARG, "cell %lld, objective %d: bound index out of range (%d, %d; %d bounds)", (long long)k, j,
+                    (int)lo, (int)hi, n_bounds[j]);
+      if (lo > hi)
+        return fail(h, TGP_ERR_ARG, "cell %lld, objective %d: the lower bound lies above the upper bound", (long long)k, j);
+      hc[(size_t)k * P + j] = (uint32_t)lo | ((uint32_t)hi << 16);
+    }
+  if (int rc = set_device(h)) return rc;
+  h->ehvi_K = 0;
+  const size_t bbytes = hb.size() * sizeof(double);
+  HIPCHK(h, h->d_ehvi.reserve(bbytes + hc.size() * sizeof(uint32_t)));
+  HIPCHK(h, hipMemcpyAsync(h->d_ehvi.p, hb.data(), bbytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync((char*)h->d_ehvi.p + bbytes, hc.data(), hc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the host vectors go away on return
+  h->ehvi_P = P;
+  h->ehvi_V = V;
+  for (int j = 0; j < EHVI_MAX_P; ++j) h->ehvi_nb[j] = j < P ? n_bounds[j] : 0;
+  h->ehvi_K = (int)K;
+  return TGP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int ehvi_need_partition(tgp_handle h) {
+  if (h->ehvi_K == 0) return fail(h, TGP_ERR_STATE, "no hypervolume partition set: call tgp_set_ehvi_partition first");
+  return TGP_OK;
+}
+
+// the tail on device-resident moments [P][M] into dout [M], bracketed by the handle's events: enqueue only
+int ehvi_enqueue_tail(tgp_handle h, const double* dmean, const double* dvar, int64_t M, double* dout) {
+  const double* db = h->d_ehvi.as<double>();
+  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_ehvi_tail(h->stream, h->ehvi_P, h->ehvi_V, h->ehvi_nb, db, dc, h->ehvi_K, dmean, dvar, M, dout);
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return TGP_OK;
+}
+
+void ehvi_read_tail_ms(tgp_handle h) {
+  float ms = 0.f;
+  h->ehvi_tail_ms = hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess ? ms : 0.0;
+  (void)hipGetLastError();
+}
+
+// checks of the stack, the candidates staged once on the leading handle, and every member's (mean, clipped var) through
+// tgp_predict itself into the leading handle's scratch: *dmean [P][M], *dvar [P][M]
+int ehvi_stack_moments(const tgp_handle* hs, int P, const double* Xq, int64_t M, int where, const double** dXq_out,
+                       double** dmean, double** dvar) {
+  tgp_handle h = hs[0];
+  if (P < 2 || P > EHVI_MAX_P)
+    return fail(h, TGP_ERR_SHAPE, "expected hypervolume improvement takes 2..%d objectives, got %d", EHVI_MAX_P, P);
+  for (int j = 0; j < P; ++j) {
+    if (!hs[j]) return fail(h, TGP_ERR_ARG, "handle %d of the stack is NULL", j);
+    if (hs[j]->d != h->d || hs[j]->device != h->device)
+      return fail(h, TGP_ERR_ARG, "the handles of a stack must share device and input dimension (handle %d: device %d, d = %d; "
+                  "handle 0: device %d, d = %d)", j, hs[j]->device, hs[j]->d, h->device, h->d);
+  }
+  if (int rc = ehvi_need_partition(h)) return rc;
+  if (h->ehvi_P != P)
+    return fail(h, TGP_ERR_ARG, "the partition has %d objectives, the stack %d", h->ehvi_P, P);
+  for (int j = 0; j < P; ++j)
+    if (!hs[j]->have_data) return fail(h, TGP_ERR_STATE, "model %d of the stack has no data: call tgp_set_data first", j);
+  if (M == 0) return TGP_OK;  // (an empty call has run the checks)
+  if (!Xq) return fail(h, TGP_ERR_ARG, "Xq is NULL");
+  if (int rc = set_device(h)) return rc;
+  const double* dXq;
+  if (int rc = stage_in(h, h->s_in, Xq, (size_t)M * h->d, where, &dXq)) return rc;
+  if (where != TGP_DEVICE)
+    if (int rc = sync(h)) return rc;  // the other members read the staged candidates from their own streams
+  HIPCHK(h, h->s_ehvi.reserve((size_t)2 * P * M * sizeof(double)));
+  *dmean = h->s_ehvi.as<double>();
+  *dvar = *dmean + (size_t)P * M;
+  double sweep_ms = 0.0;
+  for (int j = 0; j < P; ++j) {
+    // (tgp_predict synchronises the member's stream before it returns: the tail below may run on any stream)
+    if (int rc = tgp_predict(hs[j], dXq, M, *dmean + (size_t)j * M, *dvar + (size_t)j * M, TGP_DEVICE)) {
+      if (hs[j] != h) h->err = hs[j]->err;
+      return rc;
+    }
+    if (hs[j]->last_launches > 0) {
+      double ms = 0.0;
+      (void)tgp_last_kernel_ms(hs[j], &ms, nullptr);
+      sweep_ms += ms;
+    }
+  }
+  if (int rc = set_device(h)) return rc;
+  h->ehvi_sweep_ms = sweep_ms;
+  *dXq_out = dXq;
+  return TGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tgp_ehvi_moments(tgp_handle h, const double* mean, const double* var, int64_t M, double* out, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = ehvi_need_partition(h)) return rc;
+  if (M < 0) return fail(h, TGP_ERR_SHAPE, "M must be >= 0");
+  if (M == 0) return TGP_OK;
+  if (!mean || !var || !out) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  const double *dmean, *dvar;
+  double* dout;
+  if (int rc = stage_in(h, h->s_out1, mean, (size_t)h->ehvi_P * M, where, &dmean)) return rc;
+  if (int rc = stage_in(h, h->s_out2, var, (size_t)h->ehvi_P * M, where, &dvar)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out3, out, M, where, &dout)) return rc;
+  if (int rc = ehvi_enqueue_tail(h, dmean, dvar, M, dout)) return rc;
+  if (int rc = stage_out_finish(h, dout, out, M, where)) return rc;
+  if (int rc = sync(h)) return rc;
+  HIPCHK(h, hipGetLastError());
+  ehvi_read_tail_ms(h);
+  h->ehvi_sweep_ms = 0.0;
+  h->last_ms = h->ehvi_tail_ms;
+  h->last_launches = 1;
+  return TGP_OK;
+}
+
+int tgp_ehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t M, double* out, int where) {
+  if (!hs || !hs[0]) return TGP_ERR_ARG;
+  tgp_handle h = hs[0];
+  if (M < 0) return fail(h, TGP_ERR_SHAPE, "M must be >= 0");
+  if (M > 0 && !out) return fail(h, TGP_ERR_ARG, "out is NULL");
+  const double* dXq;
+  double *dmean, *dvar, *dout;
+  if (int rc = ehvi_stack_moments(hs, P, Xq, M, where, &dXq, &dmean, &dvar)) return rc;
+  if (M == 0) return TGP_OK;
+  if (int rc = stage_out_prepare(h, h->s_out3, out, M, where, &dout)) return rc;
+  if (int rc = ehvi_enqueue_tail(h, dmean, dvar, M, dout)) return rc;
+  if (int rc = stage_out_finish(h, dout, out, M, where)) return rc;
+  if (int rc = sync(h)) return rc;
+  HIPCHK(h, hipGetLastError());
+  ehvi_read_tail_ms(h);
+  h->last_ms = h->ehvi_sweep_ms;
+  h->last_launches = P;
+  return TGP_OK;
+}
+
+int tgp_ehvi_argmax(const tgp_handle* hs, int P, const double* Xq, int64_t M, int64_t index_base, double* best_val,
+                    int64_t* best_idx, double* best_x, int where) {
+  if (!hs || !hs[0]) return TGP_ERR_ARG;
+  tgp_handle h = hs[0];
+  if (M < 1) return fail(h, TGP_ERR_SHAPE, "arg-max over an empty candidate set");
+  const double* dXq;
+  double *dmean, *dvar;
+  if (int rc = ehvi_stack_moments(hs, P, Xq, M, where, &dXq, &dmean, &dvar)) return rc;
+  HIPCHK(h, h->s_out3.reserve((size_t)M * sizeof(double)));
+  HIPCHK(h, h->s_small.reserve(64));
+  double* dvals = h->s_out3.as<double>();
+  double* fv = h->s_small.as<double>();
+  int64_t* fi = (int64_t*)(fv + 1);
+  if (int rc = ehvi_enqueue_tail(h, dmean, dvar, M, dvals)) return rc;
+  if (int rc = enqueue_topk_of_values(h, dvals, M, index_base, 1, fv, fi)) return rc;
+  double hv;
+  int64_t hi;
+  HIPCHK(h, hipMemcpyAsync(&hv, fv, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&hi, fi, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  if (int rc = sync(h)) return rc;
+  HIPCHK(h, hipGetLastError());
+  ehvi_read_tail_ms(h);
+  h->last_ms = h->ehvi_sweep_ms;
+  h->last_launches = P;
+  if (best_val) *best_val = hv;
+  if (best_idx) *best_idx = hi;
+  if (best_x) {
+    const int64_t local = hi - index_base;
+    if (local < 0 || local >= M) return fail(h, TGP_ERR_HIP, "arg-max produced no valid index (all NaN?)");
+    if (where == TGP_DEVICE)
+      HIPCHK(h, hipMemcpy(best_x, dXq + local * h->d, h->d * sizeof(double), hipMemcpyDeviceToHost));
+    else
+      memcpy(best_x, Xq + local * h->d, h->d * sizeof(double));
+  }
+  return TGP_OK;
+}
+
+int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms) {
+  if (!h) return TGP_ERR_ARG;
+  if (sweeps_ms) *sweeps_ms = h->ehvi_sweep_ms;
+  if (tail_ms) *tail_ms = h->ehvi_tail_ms;
   return TGP_OK;
 }
 

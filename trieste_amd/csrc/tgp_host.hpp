@@ -121,6 +121,12 @@ struct tgp_handle_s {
   // entropy-search tails (TGP_ACQ_MES / TGP_ACQ_GIBBON): min-value samples; GIBBON's repulsion twin
   int ent_S = 0;
   DevBuf d_ent;  // [S]
+  // expected hypervolume improvement (tgp_set_ehvi_partition): P objectives, V = the largest bound count, K cells
+  int ehvi_P = 0, ehvi_V = 0, ehvi_K = 0;
+  int ehvi_nb[tgp::EHVI_MAX_P] = {0, 0, 0, 0};
+  DevBuf d_ehvi;   // [P][V] bounds, then [K][P] packed cell words
+  DevBuf s_ehvi;   // tgp_ehvi_values / tgp_ehvi_argmax: the stack's moments, mean [P][M] then var [P][M] (16 P M bytes)
+  double ehvi_sweep_ms = 0.0, ehvi_tail_ms = 0.0;   // tgp_ehvi_last_ms
   tgp_handle rep_twin = nullptr;  // not owned: this model conditioned additionally on the pending points
   double rep_weight = 0.0;
   // when the twin is literally this model's data + m <= 16 appended rows (same hyper-parameters), its variance is

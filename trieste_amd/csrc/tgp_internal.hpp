@@ -172,6 +172,14 @@ size_t bei_grad_tail_lds_bytes(int q);
 void launch_bei_grad_tail(hipStream_t s, const double* mean, const double* cov, int64_t G, int q, const double* w1,
                           const double* w2, int S, double eta, int zero_clipped, double* val, double* gmean, double* gcov,
                           int* info);
+// expected hypervolume improvement on given moments (tgp_kernels_ehvi.hip): mean / var [P][M] objective-major, bounds [P][V]
+// (row j ascending, nb[j] valid entries; nb is a HOST array), cells [K][P] packed words lower index | upper index << 16
+constexpr int EHVI_MAX_P = 4, EHVI_MAX_BOUNDS = 512;
+constexpr int64_t EHVI_MAX_CELLS = (int64_t)1 << 21;
+int ehvi_tile_width(int P, int V);   // candidates per workgroup: the largest power of two <= 64 with 8 P V C <= 160 KiB
+size_t ehvi_lds_bytes(int P, int V);
+void launch_ehvi_tail(hipStream_t s, int P, int V, const int* nb, const double* bounds, const uint32_t* cells, int K,
+                      const double* mean, const double* var, int64_t M, double* out);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

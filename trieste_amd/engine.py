@@ -788,3 +788,110 @@ def batch_ei_value_grad(engine, Xq, w1, w2, eta: float):
     if G:
         engine._chk(engine._lib.tgp_batch_ei_value_grad(engine._h, a.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), pv, pg, a.where))
     return val, grad
+
+
+# ---- expected hypervolume improvement (tgp_ehvi_*; include/tgp.h) -----------------------------------------------------
+EHVI_MAX_P, EHVI_MAX_BOUNDS, EHVI_MAX_CELLS = _lib.EHVI_MAX_P, _lib.EHVI_MAX_BOUNDS, _lib.EHVI_MAX_CELLS
+
+
+def ehvi_tile_width(P: int, V: int) -> int:
+    """Candidates per workgroup of the EHVI kernel: the largest power of two <= 64 whose table of 8 P V C bytes fits 160 KiB
+    of LDS (V = the largest number of distinct bounds of an objective).  The kernel's 1024 threads are C lanes x 1024 / C
+    slices of the cell list."""
+    C = 64
+    while C > 1 and 8 * P * V * C > 160 * 1024:
+        C //= 2
+    return C
+
+
+def ehvi_partition_tables(lower, upper):
+    """Cell bounds (lower, upper) [K, P] as a partition returns them -> (bounds [P, Vmax] rows ascending and padded with their
+    last value, n_bounds [P] int32, lower_idx [K, P] int32, upper_idx [K, P] int32): per objective the distinct float64 values
+    of all bounds (``np.unique``: exact values, no tolerance) and every cell's positions in them."""
+    lo, up = np.asarray(lower, dtype=_NP), np.asarray(upper, dtype=_NP)
+    if lo.ndim != 2 or lo.shape != up.shape:
+        raise ValueError(f"partition bounds must be two [K, P] arrays, got {lo.shape} and {up.shape}")
+    K, P = lo.shape
+    rows, li, ui = [], np.empty((K, P), np.int32), np.empty((K, P), np.int32)
+    for j in range(P):
+        values, inverse = np.unique(np.concatenate([lo[:, j], up[:, j]]), return_inverse=True)
+        rows.append(values)
+        li[:, j], ui[:, j] = inverse[:K], inverse[K:]
+    n = np.array([len(r) for r in rows], dtype=np.int32)
+    bounds = np.empty((P, max(int(n.max()), 1) if P else 1), dtype=_NP)
+    for j, r in enumerate(rows):
+        bounds[j, : len(r)] = r
+        bounds[j, len(r):] = r[-1] if len(r) else 0.0
+    return bounds, n, li, ui
+
+
+def ehvi_set_partition_tables(engine, bounds, n_bounds, lower_idx, upper_idx) -> None:
+    """Install the partition in table form (tgp_set_ehvi_partition): bounds [P, Vmax], n_bounds [P], indices [K, P]."""
+    b = np.ascontiguousarray(bounds, dtype=_NP)
+    n = np.ascontiguousarray(n_bounds, dtype=np.int32)
+    li = np.ascontiguousarray(lower_idx, dtype=np.int32)
+    ui = np.ascontiguousarray(upper_idx, dtype=np.int32)
+    if b.ndim != 2 or n.shape != (b.shape[0],) or li.ndim != 2 or li.shape != ui.shape or li.shape[1] != b.shape[0]:
+        raise ValueError(f"bounds must be [P, Vmax], n_bounds [P] and the indices [K, P], got {b.shape}, {n.shape}, "
+                         f"{li.shape} and {ui.shape}")
+    engine._ehvi_owner = None   # whichever function object installed the previous partition no longer owns the engine's
+    engine._chk(engine._lib.tgp_set_ehvi_partition(engine._h, int(b.shape[0]), b.ctypes.data, int(b.shape[1]), n.ctypes.data,
+                                                   li.ctypes.data, ui.ctypes.data, int(li.shape[0])))
+
+
+def ehvi_set_partition(engine, lower, upper) -> None:
+    """Install the cells (lower, upper) [K, P] of the non-dominated region on ``engine`` -- the LEADING engine of the stack, the
+    one :func:`ehvi_values` / :func:`ehvi_argmax` are called with first.  ``None`` or K = 0 clears the state."""
+    if lower is None or np.asarray(lower).shape[0] == 0:
+        engine._ehvi_owner = None
+        engine._chk(engine._lib.tgp_set_ehvi_partition(engine._h, 0, None, 0, None, None, None, 0))
+        return
+    ehvi_set_partition_tables(engine, *ehvi_partition_tables(lower, upper))
+
+
+def ehvi_moments(engine, mean, var):
+    """The EHVI tail on caller-supplied moments: mean, var [P, M] objective-major (host arrays or CUDA tensors) -> [M]
+    (tgp_ehvi_moments).  Needs a partition on the engine and no data."""
+    m, v = _Arg(mean), _Arg(var)
+    if len(m.shape) != 2 or m.shape != v.shape:
+        raise ValueError(f"mean and var must both be [P, M], got {m.shape} and {v.shape}")
+    if m.where != v.where:
+        raise ValueError("mean and var must live in the same place (both host or both device)")
+    out, po = GPEngine._out(m, (m.shape[1],))
+    engine._chk(engine._lib.tgp_ehvi_moments(engine._h, m.ptr, v.ptr, int(m.shape[1]), po, m.where))
+    return out
+
+
+def _handles(engines):
+    engines = list(engines)
+    if not engines:
+        raise ValueError("a stack needs at least one engine")
+    return engines, (C.c_void_p * len(engines))(*[e._h.value if hasattr(e._h, "value") else e._h for e in engines])
+
+
+def ehvi_values(engines, Xq):
+    """engines: one :class:`GPEngine` per objective (the first carries the partition); Xq [..., d] -> EHVI [...]: every
+    engine's ``predict`` and the tail in one device call (tgp_ehvi_values)."""
+    engines, hs = _handles(engines)
+    a, lead, M = engines[0]._flat(Xq)
+    out, po = GPEngine._out(a, lead)
+    engines[0]._chk(engines[0]._lib.tgp_ehvi_values(hs, len(engines), a.ptr, M, po, a.where))
+    return out
+
+
+def ehvi_argmax(engines, Xq, index_base: int = 0):
+    """-> (best EHVI, global index, best point [d] as numpy) over the candidates Xq [M, d]; the first index wins ties."""
+    engines, hs = _handles(engines)
+    a, _, M = engines[0]._flat(Xq)
+    bv, bi = C.c_double(), C.c_int64()
+    bx = np.empty(engines[0].d)
+    engines[0]._chk(engines[0]._lib.tgp_ehvi_argmax(hs, len(engines), a.ptr, M, int(index_base), C.byref(bv), C.byref(bi),
+                                                    bx.ctypes.data, a.where))
+    return bv.value, bi.value, bx
+
+
+def ehvi_last_ms(engine):
+    """(summed time of the posterior sweeps, time of the tail kernel) of the engine's most recent EHVI call, in ms."""
+    s, t = C.c_double(), C.c_double()
+    engine._chk(engine._lib.tgp_ehvi_last_ms(engine._h, C.byref(s), C.byref(t)))
+    return s.value, t.value

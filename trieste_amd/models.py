@@ -725,3 +725,51 @@ class FantasizedGaussianProcessRegression(GaussianProcessRegression):
 
     def optimize(self, dataset: Dataset):
         raise NotImplementedError("a fantasized model is not trainable; optimize its base model")
+
+
+# ---- stacks of independent models (reference models/interfaces.py:337-442) ------------------------------------------
+class ModelStack:
+    """Several single-output models presented as one multi-output model: ``predict`` and ``sample`` concatenate the members'
+    outputs on the event axis, in the order given.  Members are (model, event size) pairs; on this engine every event size
+    is 1 (one exact GPR per output)."""
+
+    def __init__(self, model_with_event_size, *models_with_event_sizes):
+        pairs = (model_with_event_size,) + models_with_event_sizes
+        self._models, self._event_sizes = zip(*pairs)
+        if any(int(size) != 1 for size in self._event_sizes):
+            raise ValueError(f"every model of a stack has event size 1 on this engine, got {list(self._event_sizes)}")
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}({', '.join(repr(pair) for pair in zip(self._models, self._event_sizes))})"
+
+    def predict(self, query_points):
+        """[..., D] -> (mean, var), each [..., number of models]."""
+        means, variances = zip(*[model.predict(query_points) for model in self._models])
+        return np.concatenate([np.asarray(m) for m in means], axis=-1), \
+            np.concatenate([np.asarray(v) for v in variances], axis=-1)
+
+    def sample(self, query_points, num_samples: int):
+        """[..., N, D] -> [..., S, N, number of models]."""
+        return np.concatenate([np.asarray(model.sample(query_points, num_samples)) for model in self._models], axis=-1)
+
+    def log(self, dataset: Optional[Dataset] = None) -> None:
+        for model in self._models:
+            model.log(dataset)
+
+
+class TrainableModelStack(ModelStack):
+    """A stack whose ``update`` and ``optimize`` hand every member the query points with its own column of the
+    observations."""
+
+    def _split(self, dataset: Dataset):
+        obs = np.asarray(dataset.observations)
+        if obs.shape[-1] != len(self._models):
+            raise ValueError(f"observations have {obs.shape[-1]} columns, the stack has {len(self._models)} models")
+        return [Dataset(dataset.query_points, obs[..., j:j + 1]) for j in range(len(self._models))]
+
+    def update(self, dataset: Dataset) -> None:
+        for model, data in zip(self._models, self._split(dataset)):
+            model.update(data)
+
+    def optimize(self, dataset: Dataset):
+        return [model.optimize(data) for model, data in zip(self._models, self._split(dataset))]

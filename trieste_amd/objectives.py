@@ -206,6 +206,16 @@ def trid_10(x):
     return trid(x, 10)
 
 
+def vlmop2(x, d: int):
+    """VLMOP2 (van Veldhuizen & Lamont 1999), typically over [-2, 2]^d: [..., d] -> [..., 2], both objectives to be minimised
+    (reference objectives/multi_objectives.py:60-73)."""
+    x = _as(x, d, "vlmop2")
+    transl = 1.0 / math.sqrt(d)
+    y1 = 1.0 - np.exp(-np.sum((x - transl) ** 2, axis=-1))
+    y2 = 1.0 - np.exp(-np.sum((x + transl) ** 2, axis=-1))
+    return np.stack([y1, y2], axis=-1)
+
+
 class SingleObjectiveTestProblem:
     """A synthetic test function with its search space, global minimizers and minimum (:39-75)."""
 
