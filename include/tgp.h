@@ -506,10 +506,17 @@ int tgp_group_last_kernel_ms(tgp_group g, double* ms);
  * the most recent sweep-type call (predict / acq_values / acq_argmax / qei / traj_*). */
 int tgp_last_kernel_ms(tgp_handle h, double* ms, int* launches);
 /* The pruned EI arg-max (tgp_acq_argmax(_async) with TGP_ACQ_EI, float64, >= 4 x #CU candidate blocks, d <= 16):
- * of the handle's most recent arg-max the candidate blocks (128 candidates each), how many of them were given up at a
- * row-block boundary because no candidate in them could still win, and how many 256-row blocks of W those skipped.  All
- * three are 0 when that arg-max did not run the pruned kernel.  Synchronises the handle's stream. */
+ * of the handle's most recent arg-max the candidate blocks (128 candidates each), how many of them were given up because no
+ * candidate in them could still win -- by the mean screen before their first row block or at a row-block boundary -- and
+ * `row_blocks_skipped`: the 256-row blocks of W BEHIND THE FIRST that the given-up blocks did not compute (a block given up
+ * by the mean screen counts Npad / 256 - 1 here; that it did not compute the first row block either is what
+ * tgp_get_prune_screened counts).  All three are 0 when that arg-max did not run the pruned kernel.  Synchronises the
+ * handle's stream. */
 int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int64_t* row_blocks_skipped);
+/* Of the blocks given up, those given up by the mean screen: from the block's posterior means alone (EI at the prior
+ * variance cannot win), before any slab store, DMA or row block.  0 when the most recent arg-max did not run the pruned
+ * kernel, at Npad = 256 (one row block: nothing is given up) and under tgp_set_variant bit 12.  Synchronises the stream. */
+int tgp_get_prune_screened(tgp_handle h, int64_t* screened);
 /* Arithmetic of the plain posterior sweeps (tgp_predict / tgp_acq_values / tgp_acq_argmax(_async) / tgp_acq_topk;
  * joint-mode, gradients, trajectories and `update` always run in float64):
  *   TGP_PREC_F64  (default) W K* on the float64 matrix cores -- the parity path;
@@ -587,7 +594,10 @@ int tgp_get_auto_strata(tgp_handle h, int64_t* checked2, int64_t* violations2, d
  * <= 2048 points through a sweep launch and tgp_predict_joint / tgp_qei / tgp_reparam_samples of <= 2048 points (groups x q) through
  * the joint kernel (rounds 1 - 5) instead of skinny triangular products (round 6: the default when no sweep / joint policy bit is
  * set -- and, for tgp_predict, no arithmetic other than float64; joint mode is float64 on every path), bit 11 = the fused EI
- * arg-max sweeps every candidate block to the end instead of giving up blocks that cannot win (same winner, bit for bit).  Bits 0-3, 7, 8: every
+ * arg-max sweeps every candidate block to the end instead of giving up blocks that cannot win (same winner, bit for bit), bit 12 =
+ * the pruned EI arg-max without the seed and the mean screen (blocks are given up at row-block boundaries only), bit 13 = its
+ * workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter (bits 12, 13: A/B runs and tests; the
+ * same winner, bit for bit, under every combination).  Bits 0-3, 7, 8: every
  * setting computes the same arithmetic on every candidate / matrix entry, bit for bit; bits 4 - 6, 9: the same values up to the
  * rounding of another summation order (bit 10 as well). */
 int tgp_set_variant(tgp_handle h, int variant);

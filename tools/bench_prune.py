@@ -2,7 +2,8 @@
 
 Two thresholds with the engine calls of bench.py's step: the model's eta (blocks are given up: the gain, with the
 counters of one step) and eta = -1e6 (every EI is 0, nothing can be given up: what the pruned kernel's generate-first
-phase and its checkpoints cost when they buy nothing).  --variant 2048 runs the unpruned kernel for the comparison; on a
+phase and its checkpoints cost when they buy nothing).  --variant 2048 runs the unpruned kernel for the comparison, 4096 the pruned one
+without the seed and the mean screen, 8192 with blocks dealt statically (and 4096 | 8192 both); on a
 tree without the pruned kernel the counters are left out (TGP_TREE=<checkout> imports the package of another checkout,
 e.g. the parent commit's, for the same-box comparison).
     python tools/bench_prune.py [--variant 2048] [--steps 10] [--warmup 3] [--workload headline|c2]"""
@@ -49,4 +50,6 @@ for label, eta in (("eta", eng.eta()), ("eta=-1e6", -1e6)):
                best_value=best[0], best_index=best[1])
     if hasattr(E, "prune_counters"):
         out["blocks, given up, row blocks skipped"] = E.prune_counters(eng)
+    if hasattr(E, "prune_screened"):
+        out["screened"] = E.prune_screened(eng)
     print(json.dumps(out), flush=True)

@@ -163,7 +163,10 @@ void apply_penalization(tgp_handle h, double* dvals, const double* dXq, int64_t 
 //   VARIANT_DAG_ONE_CHAIN (512): the persistent `update` kernel's chain as ONE workgroup (rounds 3 - 5) instead of round 6's two
 constexpr int VARIANT_NO_SPLIT = 1, VARIANT_FORCE_SPLIT = 2, VARIANT_JOINT_V1 = 4, VARIANT_REG_STAGING = 8, VARIANT_NO_DAG = 16,
               VARIANT_DAG_SMALL = 32, VARIANT_NO_REPAIR_PRODUCT = 64, VARIANT_STATIC_BLOCKS = 128, VARIANT_DAG_WHOLE_TILES = 256,
-              VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024, VARIANT_NO_PRUNE = 2048;
+              VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024, VARIANT_NO_PRUNE = 2048,
+              VARIANT_PRUNE_NO_SCREEN = 4096, VARIANT_PRUNE_STATIC_BLOCKS = 8192;
+//   VARIANT_PRUNE_NO_SCREEN (4096): the pruned EI arg-max without the seed and the mean screen (blocks are given up at checkpoints only)
+//   VARIANT_PRUNE_STATIC_BLOCKS (8192): its workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter
 //   VARIANT_SWEEP_SMALL_PREDICT (1024): tgp_predict at <= 2048 points through a sweep launch (rounds 1 - 5) instead of the skinny product
 constexpr int64_t REPAIR_PCAP = 512;   // TGP_PREC_AUTO: lists up to this many candidates are recomputed as a product
 int gemm_tall(tgp_handle h, bool tb, int m, int n, int k, double alpha, const double* A, int64_t lda, const double* B,
@@ -606,13 +609,14 @@ hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
     const bool prune = a.acq_kind == TGP_ACQ_EI && a.blk_val && !a.acq_out && !a.mean_out && !a.var_out &&
                        !(h->variant & VARIANT_NO_PRUNE);
     if (prune) {
-      ea = h->s_prune.reserve(3 * sizeof(unsigned long long));
+      ea = h->s_prune.reserve(5 * sizeof(unsigned long long));
       if (ea != hipSuccess) return ea;
       am.prune = h->s_prune.as<unsigned long long>();
+      am.prune_flags = ((h->variant & VARIANT_PRUNE_NO_SCREEN) ? 1 : 0) | ((h->variant & VARIANT_PRUNE_STATIC_BLOCKS) ? 2 : 0);
     }
     (void)hipEventRecord(h->ev0, h->stream);
     if (prune) {
-      e = hipMemsetAsync(am.prune, 0, 3 * sizeof(unsigned long long), h->stream);
+      e = hipMemsetAsync(am.prune, 0, 5 * sizeof(unsigned long long), h->stream);
       if (e != hipSuccess) return e;
       h->prune_blocks = grid;
       switch (h->kind) {
@@ -3175,17 +3179,31 @@ int tgp_stream_synchronize(tgp_handle h) {
   return TGP_OK;
 }
 
-int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int64_t* row_blocks_skipped) {
-  if (!h) return TGP_ERR_ARG;
-  unsigned long long w[3] = {0, 0, 0};
+static int read_prune_words(tgp_handle h, unsigned long long (&w)[4]) {
+  for (auto& x : w) x = 0;
   if (h->prune_blocks > 0) {
     if (int rc = set_device(h)) return rc;
     HIPCHK(h, hipMemcpyAsync(w, h->s_prune.p, sizeof w, hipMemcpyDeviceToHost, h->stream));
     if (int rc = sync(h)) return rc;
   }
+  return TGP_OK;
+}
+
+int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int64_t* row_blocks_skipped) {
+  if (!h) return TGP_ERR_ARG;
+  unsigned long long w[4];
+  if (int rc = read_prune_words(h, w)) return rc;
   if (blocks) *blocks = h->prune_blocks;
   if (given_up) *given_up = (int64_t)w[1];
   if (row_blocks_skipped) *row_blocks_skipped = (int64_t)w[2];
+  return TGP_OK;
+}
+
+int tgp_get_prune_screened(tgp_handle h, int64_t* screened) {
+  if (!h) return TGP_ERR_ARG;
+  unsigned long long w[4];
+  if (int rc = read_prune_words(h, w)) return rc;
+  if (screened) *screened = (int64_t)w[3];
   return TGP_OK;
 }
 

@@ -49,6 +49,8 @@ struct SweepArgs {
   double* var_out;    // [M] or null
   double* acq_out;    // [M] or null
   int acq_kind;       // -1: none
+  int prune_flags;    // PRUNE instantiation of sweep_dma_kernel only: 1 = no seed and no mean screen, 2 = blocks i, i + #WG, ...
+                      // (sits in what was padding: the layout of every other field is what it was)
   double acq_param;
   double* blk_val;    // [grid] or null : per-workgroup best acquisition value
   int64_t* blk_idx;   // [grid]
@@ -62,7 +64,8 @@ struct SweepArgs {
   const double* i8_rs; // int8 sweep: [Npad] row scales S_i = 2 max_k |W_ik|
   const double* i8_xsa; // int8 sweep: [Npad / 32] tiles (32 rows of Xs + alpha) for LDS staging, or null (scalar loads)
   unsigned* blk_ctr;    // sweep_i8_kernel: a workgroup's candidate blocks after its first are drawn from this counter (zero at
-                        // launch); null: blocks i, i + #WG, ...  (sweep_dma_kernel, 8 ms per block: measured neutral, not wired)
+                        // launch); null: blocks i, i + #WG, ...  (sweep_dma_kernel, 8 ms per block: measured neutral, not wired;
+                        // its PRUNE instantiation, whose blocks differ by a factor 25, draws from prune[4])
   double* aslab;      // [grid][Npad][128] C = W K* slabs of joint mode (device scratch)
   // row-group split of small sweeps (SPLIT instantiation): group g of a candidate block owns the row
   // blocks [split_ib[g], split_ib[g+1]) of W and leaves partial (mean, sum c^2) in `part`
@@ -88,9 +91,11 @@ struct SweepArgs {
                           // repair pass over the flagged candidates is enqueued without a host round trip)
   double* xqw;            // wide sweeps (dp > MAX_D): [grid][dp][128] per-workgroup scaled candidate coordinates (device
                           // scratch beside the K* slabs; the narrow instantiations keep them in LDS)
-  // the pruned EI arg-max (PRUNE instantiation of sweep_dma_kernel): [0] the bits of the best finished block maximum
-  // (EI >= 0: unsigned order is value order), [1] candidate blocks given up, [2] row blocks they skipped; ALL ZERO at
-  // launch (memset before every launch: a stale best would be a wrong result)
+  // the pruned EI arg-max (PRUNE instantiation of sweep_dma_kernel): [0] the best word: the bits of the largest of the
+  // finished block maxima and the blocks' seeds eta - mean (EI >= 0: unsigned order is value order), [1] candidate blocks
+  // given up, [2] row blocks behind the first that they did not compute, [3] blocks given up by the mean screen (they did
+  // not compute the first row block either), [4] the counter candidate blocks are drawn from; ALL ZERO at launch (memset
+  // before every launch: a stale best would be a wrong result)
   unsigned long long* prune;
 };
 constexpr double I8_TIGHT = 1.0078125;  // digit-plane scales S_i = I8_TIGHT max_k |W_ik|, S' = I8_TIGHT variance: the

@@ -25,6 +25,8 @@
 //     (271.6 ms); it is what keeps the deferred form free of scratch reloads in the every-step path (with 64-bit per-lane
 //     pointers the compiler spills one and reloads it in front of the DMA: 283 ms -- a scratch reload is an
 //     s_waitcnt vmcnt(0) on everything in flight).
+#include <type_traits>
+
 #include "tgp_dev.hpp"
 #include "tgp_internal.hpp"
 
@@ -103,12 +105,26 @@ __device__ __forceinline__ void dma_kstep(v4d (&acc)[4][2], uint32_t la, uint32_
 
 // PRUNE (tgp_kernels_sweep_prune_k*.hip, the EI arg-max alone): a candidate block is given up at a row-block boundary once
 // no candidate of it can still win.  The column norms only grow, so `variance - partial norm` bounds the variance from
-// above and EI, increasing in the variance, from above with it; the bound is compared with the launch's best finished
-// block maximum (SweepArgs::prune).  For that the block's K* is generated BEFORE the step loop (same thread -> entry
-// mapping and order as generate_B: the mean is bit-identical and known before the first MFMA) and every B tile comes
-// from the slab by DMA.  The instantiations without PRUNE compile to what they were.
-constexpr int D_PRUNE_LDS = 5 * DBN + 2;   // [4][128] checkpoint norms, [128] means, two vote words
+// above and EI, increasing in the variance, from above with it; the bound is compared with the launch's best word
+// (SweepArgs::prune).  For that the block's mean is formed BEFORE the step loop by a pass that generates every K* entry
+// and stores none (same thread -> entry mapping and order as generate_B: the mean is bit-identical and known before the
+// first MFMA).  With the mean two things are known that need no MFMA at all:
+//   * the SEED: EI(mean, var) >= eta - mean for every var > 0, so the block's largest eta - mean raises the best word
+//     before any block has finished;
+//   * the MEAN SCREEN (nb > 1): the checkpoint's rule at the prior variance (empty partial norm).  A block that fails it
+//     for every candidate is reported as given up and costs no slab store, no DMA and no row block.
+// Why a seed can stand where a finished maximum stood: the seed is eta - mean to one rounding, and the tail holds
+// RTOL = 1e-5, so the device EI of the candidate that supplied it is >= seed (1 - 1e-5).  A candidate given up under
+// ub MARGIN < best has device EI <= ub (1 + 1e-5)^2 < best (1 + 1e-5)^2 / (1 + 2^-14) < seed (1 - 1e-5): strictly below
+// that candidate's value -- neither the winner nor a tie.  The best word only ever decides giving up; results come from
+// blk_val / blk_idx.  A block that survives the screen generates its K* a second time, into the slab, and every B tile
+// comes from the slab by DMA (generating in the diagonal block-steps as the plain kernel does was measured slower in
+// this instantiation, DESIGN.md 4.1).  Candidate blocks behind a workgroup's first are drawn from a counter: the
+// winner's block runs all its block-steps, a screened one a mean pass.
+// The instantiations without PRUNE compile to what they were.
+constexpr int D_PRUNE_LDS = 5 * DBN + 3;   // [4][128] checkpoint norms, [128] means, two vote words, the drawn block
 constexpr double PRUNE_MIN_BEST = 1e-280, PRUNE_MARGIN = 1.0 + 0x1p-14;
+constexpr int PRUNE_NO_SCREEN = 1, PRUNE_STATIC_BLOCKS = 2;   // SweepArgs::prune_flags (tgp_set_variant bits 12, 13)
 
 template <int KIND, int DP, bool PRUNE>
 __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
@@ -140,12 +156,25 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   double* const psred = xqs + DBN * DP;         // [4][128]
   double* const pmean = psred + 4 * DBN;        // [128]
   int* const pvote = (int*)(pmean + DBN);       // [2]
+  int64_t* const pdraw = (int64_t*)(pmean + DBN + 1);
 
   double* const kc = a.kcache + (size_t)blockIdx.x * (size_t)Npad * DBN;
   const int64_t nblk = (a.M + DBN - 1) / DBN;
   const int T = nb * (nb + 1) / 2 * DKSTEPS;
 
-  for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+  for (int64_t blk = blockIdx.x, blk_next = 0; blk < nblk; blk = PRUNE ? blk_next : blk + gridDim.x) {
+    // PRUNE, the end of a block: the next one is drawn by one thread and handed round through LDS (static order under
+    // PRUNE_STATIC_BLOCKS); the barrier is the one behind which LDS is rewritten
+    auto draw_next = [&]() {
+      if (a.prune_flags & PRUNE_STATIC_BLOCKS) {
+        blk_next = blk + gridDim.x;
+        __syncthreads();
+      } else {
+        if (tid == 0) *pdraw = (int64_t)gridDim.x + (int64_t)atomicAdd(a.prune + 4, 1ull);
+        __syncthreads();
+        blk_next = *pdraw;   // (rewritten at the next draw, behind this block's barriers)
+      }
+    };
     for (int e = tid; e < DBN * DP; e += 1024) {  // scale the block's candidates once (c-major)
       const int j = e / DP, c = e % DP;
       const int64_t cand = blk * DBN + j;
@@ -160,9 +189,12 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
     double ssq0 = 0.0, ssq1 = 0.0, macc = 0.0;
     __syncthreads();  // xqs is read by other threads below; every DMA of the previous block has been waited for
 
-    if constexpr (PRUNE) {
-      // generate first: the whole K* of the block into the slab, the mean into pmean.  Entry for entry the arithmetic of
-      // generate_B, k-steps in the order the sweep meets them
+    // PRUNE: every K* entry of the block, entry for entry the arithmetic of generate_B, k-steps in the order the sweep
+    // meets them -- folded into the mean (GEN_MEAN, the mean pass: nothing is stored), written to the slab (GEN_SLAB, a
+    // block that survived the mean screen) or both at once (one row block: there is no screen to wait for)
+    constexpr int GEN_MEAN = 1, GEN_SLAB = 2;
+    auto generate_all = [&](auto what) {
+      constexpr int WHAT = decltype(what)::value;
       double xr[DP];
 #pragma unroll
       for (int c = 0; c < DP; ++c) xr[c] = xqs[c * DBN + kcol];
@@ -183,18 +215,30 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           const double kv = kernel_from_r2<KIND>(r2[r], variance);
-          macc = fma(kv, al[r], macc);
-          kcp[r * DBN] = kv;
+          if constexpr (WHAT & GEN_MEAN) macc = fma(kv, al[r], macc);
+          if constexpr (WHAT & GEN_SLAB) kcp[r * DBN] = kv;
         }
       }
+    };
+    if constexpr (PRUNE) {
+      if (nb > 1) generate_all(std::integral_constant<int, GEN_MEAN>{});
+      else generate_all(std::integral_constant<int, GEN_MEAN | GEN_SLAB>{});
       mred[krg * 128 + kcol] = macc;   // (no DMA is in flight: A stage 0 is free)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the slab stores, before the barrier that lets the DMA read them
       __syncthreads();
+      const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN);
       if (tid < 128) {
         double m = 0.0;
 #pragma unroll
         for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
-        pmean[tid] = m + a.m.mean_const;
+        const double pm = m + a.m.mean_const;
+        pmean[tid] = pm;
+        if (screen) {   // the seed: the block's largest eta - mean over valid columns (a NaN mean posts nothing)
+          double seed = blk * DBN + tid < a.M ? a.acq_param - pm : 0.0;
+          if (!(seed > 0.0)) seed = 0.0;
+#pragma unroll
+          for (int o = 1; o < 64; o <<= 1) seed = fmax(seed, __shfl_xor(seed, o, 64));
+          if (lane == 0 && seed > 0.0) atomicMax(a.prune, (unsigned long long)__double_as_longlong(seed));
+        }
       }
       __syncthreads();   // mred is A stage 0 again
     }
@@ -297,6 +341,24 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
       __syncthreads();
       return __builtin_amdgcn_readfirstlane(pvote[0] & pvote[1]) != 0;
     };
+    if constexpr (PRUNE) {
+      // mean screen: the checkpoint's rule with an empty partial norm (ssq0 = ssq1 = 0: the bound at the prior variance)
+      if (nb > 1 && !(a.prune_flags & PRUNE_NO_SCREEN) && cannot_win()) {
+        if (tid == 0) {
+          a.blk_val[blk] = -INFINITY;   // as a block without a valid candidate
+          a.blk_idx[blk] = INT64_MAX;
+          atomicAdd(a.prune + 1, 1ull);
+          atomicAdd(a.prune + 2, (unsigned long long)(nb - 1));   // row blocks behind the first that were not computed
+          atomicAdd(a.prune + 3, 1ull);                           // ... and the first was not either
+        }
+        draw_next();
+        continue;
+      }
+      // the block goes on: its K* into the slab, every B tile comes from there by DMA
+      if (nb > 1) generate_all(std::integral_constant<int, GEN_SLAB>{});
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the slab stores, before the barrier that lets the DMA read them
+      __syncthreads();
+    }
     bool given_up = false;
     int ib = 0, kb = 0, ks = 0;        // tile t
     int ib1 = 0, kb1 = 0, ks1 = 0;     // tile t + 1
@@ -403,7 +465,7 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
           atomicAdd(a.prune + 1, 1ull);
           atomicAdd(a.prune + 2, (unsigned long long)(nb - ib));
         }
-        __syncthreads();  // LDS is rewritten by the next block
+        draw_next();  // LDS is rewritten by the next block
         continue;
       }
     }
@@ -469,7 +531,8 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
         }
       }
     }
-    __syncthreads();  // scratch / xqs are rewritten by the next block
+    if constexpr (PRUNE) draw_next();
+    else __syncthreads();  // scratch / xqs are rewritten by the next block
   }
 }
 

@@ -577,6 +577,14 @@ def prune_counters(eng: "GPEngine"):
     return b.value, g.value, r.value
 
 
+def prune_screened(eng: "GPEngine"):
+    """Of the blocks given up in ``eng``'s most recent arg-max, those given up by the mean screen, before their first row
+    block (tgp_get_prune_screened); 0 when it did not run the pruned EI sweep.  Synchronises the engine's stream."""
+    s = C.c_int64()
+    eng._chk(eng._lib.tgp_get_prune_screened(eng._h, C.byref(s)))
+    return s.value
+
+
 class Trajectory:
     """B decoupled trajectories sharing one RFF basis (tgp_traj_*)."""
 
