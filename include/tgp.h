@@ -517,6 +517,20 @@ int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int
  * variance cannot win), before any slab store, DMA or row block.  0 when the most recent arg-max did not run the pruned
  * kernel, at Npad = 256 (one row block: nothing is given up) and under tgp_set_variant bit 12.  Synchronises the stream. */
 int tgp_get_prune_screened(tgp_handle h, int64_t* screened);
+/* Models of more than one row block (Npad > 256) run the pruned arg-max in three phases: the mean pass of every block, the
+ * blocks that survive the mean screen, a fold of what the split survivors left.  When at most `max_survivors`
+ * blocks survive, each is cut into up to `max_groups` contiguous ranges of row blocks and the ranges are spread over the
+ * workgroups (split regime); otherwise every survivor runs whole on one workgroup.  Results are the same bits either way.
+ *   max_survivors: -1 (default) the derived cap -- half the workgroups, and no more than fit a dump area of 1 GiB at 256 KiB
+ *                  per survivor and row block; 0 never split; larger values are clamped to one survivor per workgroup and to
+ *                  the dump bound;
+ *   max_groups:    0 (default) up to Npad / 256 ranges per block, never more than #workgroups / survivors.
+ * A test and A/B aid; takes effect with the next arg-max. */
+int tgp_set_prune_split(tgp_handle h, int max_survivors, int max_groups);
+/* Of the handle's most recent arg-max: `survivors`, the blocks left by the mean screen (all blocks under tgp_set_variant
+ * bit 12), and `items`, the (survivor, range) work items of the split regime, 0 in the whole-block regime.  Both are 0 when
+ * that arg-max did not run the pruned kernel or the model has one row block.  Synchronises the handle's stream. */
+int tgp_get_prune_split(tgp_handle h, int64_t* survivors, int64_t* items);
 /* Arithmetic of the plain posterior sweeps (tgp_predict / tgp_acq_values / tgp_acq_argmax(_async) / tgp_acq_topk;
  * joint-mode, gradients, trajectories and `update` always run in float64):
  *   TGP_PREC_F64  (default) W K* on the float64 matrix cores -- the parity path;

@@ -5,8 +5,9 @@ counters of one step) and eta = -1e6 (every EI is 0, nothing can be given up: wh
 phase and its checkpoints cost when they buy nothing).  --variant 2048 runs the unpruned kernel for the comparison, 4096 the pruned one
 without the seed and the mean screen, 8192 with blocks dealt statically (and 4096 | 8192 both); on a
 tree without the pruned kernel the counters are left out (TGP_TREE=<checkout> imports the package of another checkout,
-e.g. the parent commit's, for the same-box comparison).
-    python tools/bench_prune.py [--variant 2048] [--steps 10] [--warmup 3] [--workload headline|c2]"""
+e.g. the parent commit's, for the same-box comparison).  Each line carries the survivors of the list screen and the split
+work items (0: the survivors ran whole); --max-survivors 0 switches the split regime off, --max-groups caps the ranges per block.
+    python tools/bench_prune.py [--variant 2048] [--steps 10] [--warmup 3] [--workload headline|c2] [--max-survivors N] [--max-groups G]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.environ.get("TGP_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -23,11 +24,15 @@ ap.add_argument("--variant", type=int, default=0)
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--workload", default="headline", choices=sorted(SHAPES))
+ap.add_argument("--max-survivors", type=int, default=-1, help="tgp_set_prune_split: -1 derived, 0 never split")
+ap.add_argument("--max-groups", type=int, default=0, help="tgp_set_prune_split: ranges per surviving block, 0 up to the row blocks")
 args = ap.parse_args()
 obj, d, kernel, N, M, noise = SHAPES[args.workload]
 X, Y = O.synthetic_problem(getattr(O, obj), d, N)
 eng = GPEngine(d, kernel)
 eng.set_variant(args.variant)
+if hasattr(E, "set_prune_split"):
+    E.set_prune_split(eng, args.max_survivors, args.max_groups)
 eng.use_torch_stream()
 eng.set_hyper(1.0, O.default_lengthscales(d), noise, float(Y.mean()))
 eng.set_data(X, Y)
@@ -52,4 +57,6 @@ for label, eta in (("eta", eng.eta()), ("eta=-1e6", -1e6)):
         out["blocks, given up, row blocks skipped"] = E.prune_counters(eng)
     if hasattr(E, "prune_screened"):
         out["screened"] = E.prune_screened(eng)
+    if hasattr(E, "prune_split"):
+        out["survivors, items"] = E.prune_split(eng)
     print(json.dumps(out), flush=True)

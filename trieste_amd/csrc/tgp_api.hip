@@ -30,10 +30,10 @@ hipError_t launch_sweep_dma_kind0(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_sweep_dma_kind1(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_sweep_dma_kind2(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_sweep_dma_kind3(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_prune_kind0(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_prune_kind1(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_prune_kind2(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_prune_kind3(hipStream_t, const SweepArgs&, int64_t);
+hipError_t launch_sweep_prune_kind0(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
+hipError_t launch_sweep_prune_kind1(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
+hipError_t launch_sweep_prune_kind2(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
+hipError_t launch_sweep_prune_kind3(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
 hipError_t launch_joint_kind0(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_joint_kind1(hipStream_t, const SweepArgs&, int64_t);
 hipError_t launch_joint_kind2(hipStream_t, const SweepArgs&, int64_t);
@@ -608,22 +608,35 @@ hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
     // at a row-block boundary (PRUNE instantiation; the same winner bit for bit)
     const bool prune = a.acq_kind == TGP_ACQ_EI && a.blk_val && !a.acq_out && !a.mean_out && !a.var_out &&
                        !(h->variant & VARIANT_NO_PRUNE);
+    PruneLaunch pl{0, 0, 8};
     if (prune) {
-      ea = h->s_prune.reserve(5 * sizeof(unsigned long long));
+      // more than one row block: three phases; the split cap on S and with it the dump area follow from the bound on the dump
+      // (no more than PRUNE_DUMP_MAX_BYTES, no more than the K* slabs: at most one survivor per workgroup), DESIGN.md 4.1
+      const int nb = (int)(a.m.Npad / NPAD_MULT);
+      size_t words = PRUNE_HDR_WORDS;
+      if (nb > 1) {
+        const int64_t hard = std::min<int64_t>(wg, (int64_t)(PRUNE_DUMP_MAX_BYTES / ((size_t)nb * PRUNE_DUMP_BLOCK * sizeof(double))));
+        pl.max_survivors = (int)(h->prune_max_survivors < 0 ? std::min<int64_t>(hard, wg / 2) : std::min<int64_t>(hard, h->prune_max_survivors));
+        pl.max_groups = h->prune_max_groups;
+        static const bool mean4 = getenv("TGP_PRUNE_MEAN_WAVES4") != nullptr;  // A/B aid: phase 1 at four waves per SIMD
+        pl.mean_waves = mean4 ? 4 : 8;
+        words = prune_dump_word(grid) + (size_t)pl.max_survivors * nb * PRUNE_DUMP_BLOCK;
+      }
+      ea = h->s_prune.reserve(words * sizeof(unsigned long long));
       if (ea != hipSuccess) return ea;
       am.prune = h->s_prune.as<unsigned long long>();
       am.prune_flags = ((h->variant & VARIANT_PRUNE_NO_SCREEN) ? 1 : 0) | ((h->variant & VARIANT_PRUNE_STATIC_BLOCKS) ? 2 : 0);
     }
     (void)hipEventRecord(h->ev0, h->stream);
     if (prune) {
-      e = hipMemsetAsync(am.prune, 0, 5 * sizeof(unsigned long long), h->stream);
+      e = hipMemsetAsync(am.prune, 0, PRUNE_HDR_WORDS * sizeof(unsigned long long), h->stream);
       if (e != hipSuccess) return e;
       h->prune_blocks = grid;
       switch (h->kind) {
-        case TGP_RBF: e = launch_sweep_prune_kind0(h->stream, a, wg); break;
-        case TGP_MATERN12: e = launch_sweep_prune_kind1(h->stream, a, wg); break;
-        case TGP_MATERN32: e = launch_sweep_prune_kind2(h->stream, a, wg); break;
-        default: e = launch_sweep_prune_kind3(h->stream, a, wg); break;
+        case TGP_RBF: e = launch_sweep_prune_kind0(h->stream, a, wg, pl); break;
+        case TGP_MATERN12: e = launch_sweep_prune_kind1(h->stream, a, wg, pl); break;
+        case TGP_MATERN32: e = launch_sweep_prune_kind2(h->stream, a, wg, pl); break;
+        default: e = launch_sweep_prune_kind3(h->stream, a, wg, pl); break;
       }
     } else {
       switch (h->kind) {
@@ -3196,6 +3209,27 @@ int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int
   if (blocks) *blocks = h->prune_blocks;
   if (given_up) *given_up = (int64_t)w[1];
   if (row_blocks_skipped) *row_blocks_skipped = (int64_t)w[2];
+  return TGP_OK;
+}
+
+int tgp_set_prune_split(tgp_handle h, int max_survivors, int max_groups) {
+  if (!h || max_survivors < -1 || max_groups < 0) return TGP_ERR_ARG;
+  h->prune_max_survivors = max_survivors;
+  h->prune_max_groups = max_groups;
+  return TGP_OK;
+}
+
+int tgp_get_prune_split(tgp_handle h, int64_t* survivors, int64_t* items) {
+  if (!h) return TGP_ERR_ARG;
+  unsigned long long w[8];
+  for (auto& x : w) x = 0;
+  if (h->prune_blocks > 0) {
+    if (int rc = set_device(h)) return rc;
+    HIPCHK(h, hipMemcpyAsync(w, h->s_prune.p, sizeof w, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sync(h)) return rc;
+  }
+  if (survivors) *survivors = (int64_t)w[PRUNE_W_SURVIVORS];
+  if (items) *items = (int64_t)w[PRUNE_W_ITEMS];
   return TGP_OK;
 }
 

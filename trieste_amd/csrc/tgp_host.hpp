@@ -107,8 +107,9 @@ struct tgp_handle_s {
                                  // hyper-parameters in effect at the next SWEEP stay within a factor two of these
   bool auto_hyper_dirty = false; // tgp_set_hyper ran since the last sweep: the keep-or-restart decision is taken at the next
                                  // sweep (a fit's trial evaluations move the hyper-parameters far and back again)
-  DevBuf s_prune;          // the pruned EI arg-max: best word, three counters, draw counter (SweepArgs::prune)
+  DevBuf s_prune;          // the pruned EI arg-max: header words, bounds, survivor list, means, accumulator dump (SweepArgs::prune)
   int64_t prune_blocks = 0;  // candidate blocks of the most recent arg-max if it ran pruned, else 0
+  int prune_max_survivors = -1, prune_max_groups = 0;   // tgp_set_prune_split: -1 the derived split cap, 0 never split; 0 up to nb ranges
   DevBuf s_rep, s_rep_stats, s_blkctr;   // (s_blkctr: the int8 sweep's candidate-block counter, one word)
   DevBuf d_wq, d_rs, d_xsa;
   uint64_t wq_version = 0;

@@ -96,7 +96,25 @@ struct SweepArgs {
   // given up, [2] row blocks behind the first that they did not compute, [3] blocks given up by the mean screen (they did
   // not compute the first row block either), [4] the counter candidate blocks are drawn from; ALL ZERO at launch (memset
   // before every launch: a stale best would be a wrong result)
+  // Models of more than one row block run in three phases and keep more behind the same pointer: words
+  // [PRUNE_W_SURVIVORS] S, [PRUNE_W_ITEMS] split work items (0: whole-block regime), [PRUNE_W_GROUPS] ranges per survivor,
+  // [PRUNE_W_IB ..] the range boundaries; from word PRUNE_HDR_WORDS on the blocks' bounds [nblk] (double), the survivor list
+  // [nblk] (int64), the means [nblk][128] (double) and, rounded up to 32 words, the accumulator dump
+  // [survivor][row block][32][1024] (double).  Only the header is cleared per launch: everything else is written before it is read.
   unsigned long long* prune;
+};
+constexpr int PRUNE_W_SURVIVORS = 5, PRUNE_W_ITEMS = 6, PRUNE_W_GROUPS = 7, PRUNE_W_IB = 16, PRUNE_MAX_GROUPS = 64,
+              PRUNE_HDR_WORDS = 128;
+constexpr size_t PRUNE_DUMP_BLOCK = 32 * 1024;                   // doubles per (survivor, row block): 256 KiB
+constexpr size_t PRUNE_DUMP_MAX_BYTES = (size_t)1 << 30;         // the dump area never exceeds this, nor the launch's K* slabs
+inline __host__ __device__ size_t prune_dump_word(int64_t nblk) {
+  return ((size_t)PRUNE_HDR_WORDS + (size_t)nblk * (2 + SW_BN) + 31) / 32 * 32;
+}
+// the three-phase launch of the pruned EI arg-max (tgp_kernels_sweep_dma.inc): the effective knobs of tgp_set_prune_split
+struct PruneLaunch {
+  int max_survivors;   // split cap on S after clamping (0: never split); the dump area holds this many survivors
+  int max_groups;      // cap on ranges per survivor (0: up to the row blocks)
+  int mean_waves;      // phase 1: waves per SIMD it is compiled for (8 or 4)
 };
 constexpr double I8_TIGHT = 1.0078125;  // digit-plane scales S_i = I8_TIGHT max_k |W_ik|, S' = I8_TIGHT variance: the
                                         // balanced digits reach |q| <= 0x7f7f7f7f = 0.99609 2^31 > 2^31 / I8_TIGHT

@@ -125,6 +125,48 @@ __device__ __forceinline__ void dma_kstep(v4d (&acc)[4][2], uint32_t la, uint32_
 constexpr int D_PRUNE_LDS = 5 * DBN + 3;   // [4][128] checkpoint norms, [128] means, two vote words, the drawn block
 constexpr double PRUNE_MIN_BEST = 1e-280, PRUNE_MARGIN = 1.0 + 0x1p-14;
 constexpr int PRUNE_NO_SCREEN = 1, PRUNE_STATIC_BLOCKS = 2;   // SweepArgs::prune_flags (tgp_set_variant bits 12, 13)
+// Models of more than one row block run the pruned arg-max in THREE PHASES on one stream (DESIGN.md 4.1):
+//   1 prune_mean_kernel: the mean pass of every block -- means, seed, and the block's largest bound at the prior variance;
+//     prune_list_kernel then applies the give-up rule per block against the best word that holds EVERY seed and writes the
+//     survivors in block order (S and the order of the work are deterministic), the regime and the ranges;
+//   2 sweep_dma_kernel<.., PRUNE>: the survivors.  Whole-block regime: drawn from the list and run as ever (slab, row blocks,
+//     checkpoints, fold, tail).  Split regime (S small): one workgroup per (survivor, range of row blocks); at the end of a
+//     row block the 32 accumulator doubles of every thread go to the dump area instead of into the column norms;
+//   3 prune_fold_kernel: per split survivor the folds replayed over the dump in the fused order, then the fused tail.
+// No workgroup waits for another.  Models of one row block keep the single launch.
+constexpr int GEN_MEAN = 1, GEN_SLAB = 2;
+
+// Every K* entry of k-steps [0, gmax) of a block, entry for entry the arithmetic of generate_B, k-steps in the order the
+// sweep meets them -- folded into the mean (GEN_MEAN: nothing is stored), written to the slab (GEN_SLAB) or both.  One
+// function for the mean kernel and the sweep: the thread -> entry mapping and the order of the fma chain fix the mean's bits.
+template <int KIND, int DP, int WHAT>
+__device__ __forceinline__ void prune_generate(const SweepArgs& a, const double* xqs, int kcol, int krg, int gmax, double* kc,
+                                               double variance, double& macc) {
+  double xr[DP];
+#pragma unroll
+  for (int c = 0; c < DP; ++c) xr[c] = xqs[c * DBN + kcol];
+  for (int g = 0; g < gmax; ++g) {
+    const int64_t krow0 = (int64_t)g * DBK + 2 * krg;
+    const cptr xs = as_const(a.m.Xs + krow0 * DP);
+    const cptr al = as_const(a.m.alpha + krow0);
+    double r2[2] = {0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < DP; ++c) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const double t0 = xr[c] - xs[r * DP + c];
+        r2[r] = fma(t0, t0, r2[r]);
+      }
+    }
+    double* kcp = kc + krow0 * DBN + kcol;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const double kv = kernel_from_r2<KIND>(r2[r], variance);
+      if constexpr (WHAT & GEN_MEAN) macc = fma(kv, al[r], macc);
+      if constexpr (WHAT & GEN_SLAB) kcp[r * DBN] = kv;
+    }
+  }
+}
 
 template <int KIND, int DP, bool PRUNE>
 __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
@@ -162,17 +204,56 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   const int64_t nblk = (a.M + DBN - 1) / DBN;
   const int T = nb * (nb + 1) / 2 * DKSTEPS;
 
-  for (int64_t blk = blockIdx.x, blk_next = 0; blk < nblk; blk = PRUNE ? blk_next : blk + gridDim.x) {
+  // PRUNE, phase 2 (nb > 1): the blocks are the entries of the survivor list.  Split regime (items > 0): this workgroup
+  // is work item blockIdx.x = (survivor, range), row blocks [ib_lo, ib_hi) of the one block, and nothing else.
+  const bool listed = PRUNE && nb > 1;
+  int64_t nsurv = 0, li = blockIdx.x, blk_first = blockIdx.x;
+  int srv = 0, ib_lo = 0, ib_hi = nb;
+  bool split = false;
+  if constexpr (PRUNE) {
+    if (listed) {
+      const unsigned long long* hdr = a.prune;
+      const int64_t* list = (const int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk);
+      nsurv = (int64_t)hdr[PRUNE_W_SURVIVORS];
+      const int items = (int)hdr[PRUNE_W_ITEMS], groups = (int)hdr[PRUNE_W_GROUPS];
+      split = items > 0;
+      if (split) {
+        if ((int)blockIdx.x >= items) return;
+        srv = (int)blockIdx.x / groups;
+        const int g = (int)blockIdx.x % groups;
+        ib_lo = (int)hdr[PRUNE_W_IB + g];
+        ib_hi = (int)hdr[PRUNE_W_IB + g + 1];
+        blk_first = list[srv];
+      } else {
+        blk_first = li < nsurv ? list[li] : nblk;
+      }
+    }
+  }
+  const int Tb = PRUNE ? (ib_hi * (ib_hi + 1) / 2 - ib_lo * (ib_lo + 1) / 2) * DKSTEPS : T;   // tiles of this workgroup's block
+
+  for (int64_t blk = PRUNE ? blk_first : (int64_t)blockIdx.x, blk_next = 0; blk < nblk; blk = PRUNE ? blk_next : blk + gridDim.x) {
     // PRUNE, the end of a block: the next one is drawn by one thread and handed round through LDS (static order under
-    // PRUNE_STATIC_BLOCKS); the barrier is the one behind which LDS is rewritten
+    // PRUNE_STATIC_BLOCKS); the barrier is the one behind which LDS is rewritten.  Phase 2 draws list positions.
     auto draw_next = [&]() {
+      if (split) {
+        blk_next = nblk;   // a work item is all this workgroup does
+        __syncthreads();
+        return;
+      }
+      int64_t pos;
       if (a.prune_flags & PRUNE_STATIC_BLOCKS) {
-        blk_next = blk + gridDim.x;
+        pos = (listed ? li : blk) + gridDim.x;
         __syncthreads();
       } else {
         if (tid == 0) *pdraw = (int64_t)gridDim.x + (int64_t)atomicAdd(a.prune + 4, 1ull);
         __syncthreads();
-        blk_next = *pdraw;   // (rewritten at the next draw, behind this block's barriers)
+        pos = *pdraw;   // (rewritten at the next draw, behind this block's barriers)
+      }
+      if (listed) {
+        li = pos;
+        blk_next = pos < nsurv ? ((const int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk))[pos] : nblk;
+      } else {
+        blk_next = pos;
       }
     };
     for (int e = tid; e < DBN * DP; e += 1024) {  // scale the block's candidates once (c-major)
@@ -189,40 +270,15 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
     double ssq0 = 0.0, ssq1 = 0.0, macc = 0.0;
     __syncthreads();  // xqs is read by other threads below; every DMA of the previous block has been waited for
 
-    // PRUNE: every K* entry of the block, entry for entry the arithmetic of generate_B, k-steps in the order the sweep
-    // meets them -- folded into the mean (GEN_MEAN, the mean pass: nothing is stored), written to the slab (GEN_SLAB, a
-    // block that survived the mean screen) or both at once (one row block: there is no screen to wait for)
-    constexpr int GEN_MEAN = 1, GEN_SLAB = 2;
-    auto generate_all = [&](auto what) {
-      constexpr int WHAT = decltype(what)::value;
-      double xr[DP];
-#pragma unroll
-      for (int c = 0; c < DP; ++c) xr[c] = xqs[c * DBN + kcol];
-      for (int g = 0; g < nb * DKSTEPS; ++g) {
-        const int64_t krow0 = (int64_t)g * DBK + 2 * krg;
-        const cptr xs = as_const(a.m.Xs + krow0 * DP);
-        const cptr al = as_const(a.m.alpha + krow0);
-        double r2[2] = {0.0, 0.0};
-#pragma unroll
-        for (int c = 0; c < DP; ++c) {
-#pragma unroll
-          for (int r = 0; r < 2; ++r) {
-            const double t0 = xr[c] - xs[r * DP + c];
-            r2[r] = fma(t0, t0, r2[r]);
-          }
-        }
-        double* kcp = kc + krow0 * DBN + kcol;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const double kv = kernel_from_r2<KIND>(r2[r], variance);
-          if constexpr (WHAT & GEN_MEAN) macc = fma(kv, al[r], macc);
-          if constexpr (WHAT & GEN_SLAB) kcp[r * DBN] = kv;
-        }
-      }
-    };
+    // PRUNE: the block's means are known before its first MFMA.  Phase 2 (nb > 1) reads what the mean kernel stored;
+    // a model of one row block generates its K* here, into the mean and the slab at once (there is no screen to wait for)
     if constexpr (PRUNE) {
-      if (nb > 1) generate_all(std::integral_constant<int, GEN_MEAN>{});
-      else generate_all(std::integral_constant<int, GEN_MEAN | GEN_SLAB>{});
+      if (listed) {   // (read behind the barriers that follow the slab generation)
+        if (tid < 128) pmean[tid] = ((const double*)(a.prune + PRUNE_HDR_WORDS + 2 * nblk))[blk * DBN + tid];
+      }
+    }
+    if constexpr (PRUNE) if (!listed) {   // (one row block)
+      prune_generate<KIND, DP, GEN_MEAN | GEN_SLAB>(a, xqs, kcol, krg, nb * DKSTEPS, kc, variance, macc);
       mred[krg * 128 + kcol] = macc;   // (no DMA is in flight: A stage 0 is free)
       __syncthreads();
       const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN);
@@ -341,34 +397,39 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
       __syncthreads();
       return __builtin_amdgcn_readfirstlane(pvote[0] & pvote[1]) != 0;
     };
+    // PRUNE, split regime: a complete row block of C goes to the dump area as it stands, [survivor][row block][32][1024]
+    // (thread-linear: coalesced); prune_fold_kernel folds it in fold_block's order.  Accumulators cleared.
+    auto dump_block = [&](int ibd) {
+      double* dp = (double*)(a.prune + prune_dump_word(nblk)) + ((size_t)srv * nb + ibd) * PRUNE_DUMP_BLOCK + tid;
+#pragma unroll
+      for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dp[((fm * 2 + fn) * 4 + r) * 1024] = acc[fm][fn][r];
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the stores, and the Wt DMA in flight: the steps count what they issue)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
+    };
     if constexpr (PRUNE) {
-      // mean screen: the checkpoint's rule with an empty partial norm (ssq0 = ssq1 = 0: the bound at the prior variance)
-      if (nb > 1 && !(a.prune_flags & PRUNE_NO_SCREEN) && cannot_win()) {
-        if (tid == 0) {
-          a.blk_val[blk] = -INFINITY;   // as a block without a valid candidate
-          a.blk_idx[blk] = INT64_MAX;
-          atomicAdd(a.prune + 1, 1ull);
-          atomicAdd(a.prune + 2, (unsigned long long)(nb - 1));   // row blocks behind the first that were not computed
-          atomicAdd(a.prune + 3, 1ull);                           // ... and the first was not either
-        }
-        draw_next();
-        continue;
-      }
-      // the block goes on: its K* into the slab, every B tile comes from there by DMA
-      if (nb > 1) generate_all(std::integral_constant<int, GEN_SLAB>{});
+      // phase 2: the K* rows this workgroup's row blocks meet go into the slab, every B tile comes from there by DMA
+      // (the mean screen, today's rule at the prior variance, has run over the whole list in prune_list_kernel)
+      if (listed) prune_generate<KIND, DP, GEN_SLAB>(a, xqs, kcol, krg, ib_hi * DKSTEPS, kc, variance, macc);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the slab stores, before the barrier that lets the DMA read them
       __syncthreads();
     }
     bool given_up = false;
-    int ib = 0, kb = 0, ks = 0;        // tile t
-    int ib1 = 0, kb1 = 0, ks1 = 0;     // tile t + 1
+    int ib = PRUNE ? ib_lo : 0, kb = 0, ks = 0;        // tile t
+    int ib1 = ib, kb1 = 0, ks1 = 0;                    // tile t + 1
     advance(ib1, kb1, ks1);
     // prologue: Wt tiles 0 and 1 in flight, K* tile 0 generated (k-step (0, 0) is always a first use)
-    dma_A(0, 0, 0, 0);
+    dma_A(0, ib, 0, 0);
     if constexpr (PRUNE) dma_B(0, 0, 0);
-    if (T > 1) dma_A(1, ib1, kb1, ks1);
+    if (Tb > 1) dma_A(1, ib1, kb1, ks1);
     if constexpr (!PRUNE) generate_B(0, 0, 0);
-    if (T > 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    if (Tb > 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -385,20 +446,27 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
         dpend = false;
       }
     };
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < Tb; ++t) {
       int ib2 = ib1, kb2 = kb1, ks2 = ks1;  // tile t + 2
       advance(ib2, kb2, ks2);
-      const bool has1 = t + 1 < T, has2 = t + 2 < T;
+      const bool has1 = t + 1 < Tb, has2 = t + 2 < Tb;
       const bool gen1 = !PRUNE && has1 && kb1 == ib1;  // tile t + 1 brings K* rows seen for the first time
       if (TGP_DMA_DEFER) {
         __builtin_amdgcn_s_setprio(2);
         flush_deferred();
         __builtin_amdgcn_s_setprio(0);
         if (pend_fold) {
-          fold_block();
+          bool dumped = false;
+          if constexpr (PRUNE) {
+            if (split) {   // row block ib - 1 is complete
+              dump_block(ib - 1);
+              dumped = true;
+            }
+          }
+          if (!dumped) fold_block();
           pend_fold = false;
           if constexpr (PRUNE) {
-            if (cannot_win()) {   // row blocks ib .. nb - 1 are not needed
+            if (!split && cannot_win()) {   // row blocks ib .. nb - 1 are not needed
               given_up = true;
               break;
             }
@@ -454,6 +522,13 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
     }
     if (TGP_DMA_DEFER) {
       flush_deferred();
+      if constexpr (PRUNE) {
+        if (split) {   // the item's last row block; fold and tail are prune_fold_kernel's
+          dump_block(ib - 1);
+          draw_next();
+          continue;
+        }
+      }
       if (pend_fold) fold_block();
     }
     if constexpr (PRUNE) {
@@ -536,6 +611,223 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   }
 }
 
+#ifdef TGP_SWEEP_PRUNE_TU
+// Phase 1: the mean pass of every candidate block, blocks i, i + #WG, ... (a pass costs the same for every block).  Leaves
+// the block's 128 means, posts its seed as the fused kernel did and stores the largest EI tail at the prior variance over
+// its valid candidates (a NaN bound as +inf: never screened).  Gives nothing up.  No A / B stages, no accumulators, no
+// slab: WAVES per SIMD is 8 (two workgroups per compute unit) or 4.
+template <int KIND, int DP, int WAVES>
+__global__ __launch_bounds__(1024, WAVES) void prune_mean_kernel(const SweepArgs a) {
+  __shared__ double smem[DBN * DP + 8 * DBN + 2];
+  double* const xqs = smem;              // [DP][128]
+  double* const mred = smem + DBN * DP;  // [8][128]
+  double* const ubw = mred + 8 * DBN;    // [2]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kcol = tid & 127;
+  const int krg = __builtin_amdgcn_readfirstlane(tid >> 7);
+  const int nb = (int)(a.m.Npad / DBM);
+  const int d = a.m.d;
+  const double variance = a.m.variance;
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  double* const ubs = (double*)(a.prune + PRUNE_HDR_WORDS);
+  double* const means = (double*)(a.prune + PRUNE_HDR_WORDS + 2 * nblk);
+  const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN);
+  for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    for (int e = tid; e < DBN * DP; e += 1024) {  // scale the block's candidates once (c-major)
+      const int j = e / DP, c = e % DP;
+      const int64_t cand = blk * DBN + j;
+      const int64_t src = cand < a.M ? cand : 0;
+      xqs[c * DBN + j] = (c < d) ? a.Xq[src * d + c] / as_const(a.m.ls)[c] : 0.0;
+    }
+    __syncthreads();
+    double macc = 0.0;
+    prune_generate<KIND, DP, GEN_MEAN>(a, xqs, kcol, krg, nb * DKSTEPS, nullptr, variance, macc);
+    mred[krg * 128 + kcol] = macc;
+    __syncthreads();
+    if (tid < 128) {
+      double m = 0.0;
+#pragma unroll
+      for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
+      const double pm = m + a.m.mean_const;
+      means[blk * DBN + tid] = pm;
+      const bool valid = blk * DBN + tid < a.M;
+      if (screen) {   // the seed: the block's largest eta - mean over valid columns (a NaN mean posts nothing)
+        double seed = valid ? a.acq_param - pm : 0.0;
+        if (!(seed > 0.0)) seed = 0.0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) seed = fmax(seed, __shfl_xor(seed, o, 64));
+        if (lane == 0 && seed > 0.0) atomicMax(a.prune, (unsigned long long)__double_as_longlong(seed));
+      }
+      // the checkpoint's bound with an empty partial norm; columns past M have nothing to lose
+      double ub = -INFINITY;
+      if (valid) {
+        ub = acq_tail(ACQ_EI, a.acq_param, pm, fmax(variance, VAR_FLOOR), a.m.noise);
+        if (ub != ub) ub = INFINITY;
+      }
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) ub = fmax(ub, __shfl_xor(ub, o, 64));
+      if (lane == 0) ubw[w] = ub;
+    }
+    __syncthreads();   // xqs and mred are rewritten by the next block
+    if (tid == 0) ubs[blk] = fmax(ubw[0], ubw[1]);
+  }
+}
+
+// ranges of roughly equal triangular work over nb row blocks (plan_split of the host side); single row blocks when g == nb
+__device__ bool prune_plan(unsigned long long* ibw, int nb, int g) {
+  if (g == nb) {
+    for (int k = 0; k <= g; ++k) ibw[k] = (unsigned long long)k;
+    return true;
+  }
+  const int total = nb * (nb + 1) / 2;
+  ibw[0] = 0;
+  int ib = 0;
+  for (int k = 1; k < g; ++k) {
+    while (ib < nb && ib * (ib + 1) / 2 < (int)((int64_t)total * k / g)) ++ib;
+    const int prev = (int)ibw[k - 1] + 1;
+    ibw[k] = (unsigned long long)(ib > prev ? ib : prev);
+  }
+  ibw[g] = (unsigned long long)nb;
+  bool ok = true;
+  for (int k = 0; k < g; ++k) ok = ok && ibw[k] < ibw[k + 1];
+  return ok;
+}
+
+// Between phases 1 and 2, one workgroup: the give-up rule per block on the stored bound against the best word, which now
+// holds every seed -- best > PRUNE_MIN_BEST and ub_max MARGIN < best.  Rounding a product with a constant is monotone, so
+// the largest bound fails the test exactly when every candidate's does: the per-candidate vote of the fused screen.
+// Screened blocks get (-inf, INT64_MAX) and are counted; the survivors are listed in block order; then the regime.
+__global__ __launch_bounds__(1024) void prune_list_kernel(const SweepArgs a, const PruneLaunch pl, int wg) {
+  __shared__ int wcnt[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nb = (int)(a.m.Npad / DBM);
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  const double* ubs = (const double*)(a.prune + PRUNE_HDR_WORDS);
+  int64_t* list = (int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk);
+  const double best = __longlong_as_double((long long)a.prune[0]);
+  const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN) && best > PRUNE_MIN_BEST;
+  int64_t base = 0;
+  for (int64_t c0 = 0; c0 < nblk; c0 += 1024) {
+    const int64_t blk = c0 + tid;
+    bool live = false;
+    if (blk < nblk) {
+      live = !(screen && ubs[blk] * PRUNE_MARGIN < best);
+      if (!live) {
+        a.blk_val[blk] = -INFINITY;   // as a block without a valid candidate
+        a.blk_idx[blk] = INT64_MAX;
+      }
+    }
+    const unsigned long long vote = __ballot(live);
+    if (lane == 0) wcnt[w] = __popcll(vote);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int i = 0; i < 16; ++i) {
+      if (i < w) before += wcnt[i];
+      total += wcnt[i];
+    }
+    if (live) list[base + before + __popcll(vote & ((1ull << lane) - 1ull))] = blk;
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int64_t S = base, out = nblk - S;
+    a.prune[1] += (unsigned long long)out;
+    a.prune[2] += (unsigned long long)(out * (nb - 1));   // row blocks behind the first that are not computed
+    a.prune[3] += (unsigned long long)out;                // ... and the first is not either
+    a.prune[PRUNE_W_SURVIVORS] = (unsigned long long)S;
+    int groups = 0;
+    if (S >= 1 && S <= (int64_t)pl.max_survivors && S <= (int64_t)wg) {   // split regime
+      groups = (int)((int64_t)wg / S);
+      if (groups > nb) groups = nb;
+      if (groups > PRUNE_MAX_GROUPS) groups = PRUNE_MAX_GROUPS;
+      if (pl.max_groups > 0 && groups > pl.max_groups) groups = pl.max_groups;
+      while (!prune_plan(a.prune + PRUNE_W_IB, nb, groups)) --groups;   // (one range always works)
+    }
+    a.prune[PRUNE_W_GROUPS] = (unsigned long long)groups;
+    a.prune[PRUNE_W_ITEMS] = (unsigned long long)(S * groups);
+  }
+}
+
+// Phase 3, one workgroup per split survivor: thread (wave, lane) replays fold_block over its dumped accumulators for
+// ib = 0 .. nb - 1 in the fused order (fm, r; explicit fma), then the fused kernel's reduction and tail on the stored means.
+// The accumulators of a row block do not depend on where a work item started: the variance has the fused kernel's bits.
+__global__ __launch_bounds__(1024) void prune_fold_kernel(const SweepArgs a) {
+  __shared__ double sred[4 * DBN];
+  __shared__ double bvs[2];
+  __shared__ int64_t bis[2];
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  if (a.prune[PRUNE_W_ITEMS] == 0 || (unsigned long long)blockIdx.x >= a.prune[PRUNE_W_SURVIVORS]) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = w >> 2, wn = w & 3;
+  const int nb = (int)(a.m.Npad / DBM);
+  const int64_t blk = ((const int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk))[blockIdx.x];
+  const double* means = (const double*)(a.prune + PRUNE_HDR_WORDS + 2 * nblk);
+  const double* dp = (const double*)(a.prune + prune_dump_word(nblk)) + (size_t)blockIdx.x * nb * PRUNE_DUMP_BLOCK + tid;
+  double ssq0 = 0.0, ssq1 = 0.0;
+  for (int ib = 0; ib < nb; ++ib, dp += PRUNE_DUMP_BLOCK) {
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double c0 = dp[((fm * 2 + 0) * 4 + r) * 1024], c1 = dp[((fm * 2 + 1) * 4 + r) * 1024];
+        ssq0 = fma(c0, c0, ssq0);
+        ssq1 = fma(c1, c1, ssq1);
+      }
+  }
+  {
+    double s0 = ssq0, s1 = ssq1;
+    s0 += __shfl_xor(s0, 16, 64);
+    s0 += __shfl_xor(s0, 32, 64);
+    s1 += __shfl_xor(s1, 16, 64);
+    s1 += __shfl_xor(s1, 32, 64);
+    if (lane < 16) {
+      sred[wm * 128 + wn * 32 + lane] = s0;
+      sred[wm * 128 + wn * 32 + 16 + lane] = s1;
+    }
+  }
+  __syncthreads();
+  double val = -INFINITY;
+  int64_t gidx = INT64_MAX;
+  if (tid < 128) {
+    const int64_t cj = blk * DBN + tid;
+    if (cj < a.M) {
+      const double mean = means[cj];
+      const double s = (sred[tid] + sred[128 + tid]) + (sred[256 + tid] + sred[384 + tid]);
+      const double var = fmax(a.m.variance - s, VAR_FLOOR);
+      const double v = acq_tail(a.acq_kind, a.acq_param, mean, var, a.m.noise);
+      if (!(v != v)) {
+        val = v;
+        gidx = a.index_base + cj;
+      }
+    }
+    wave_argmax(val, gidx);
+    if (lane == 0) {
+      bvs[w] = val;
+      bis[w] = gidx;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double v0 = bvs[0];
+    int64_t i0 = bis[0];
+    if (better(bvs[1], bis[1], v0, i0)) {
+      v0 = bvs[1];
+      i0 = bis[1];
+    }
+    a.blk_val[blk] = v0;
+    a.blk_idx[blk] = i0;
+  }
+}
+
+template <int KIND, int DP>
+void launch_prune_mean(hipStream_t s, const SweepArgs& a, int64_t wg, int waves) {
+  if (waves >= 8) hipLaunchKernelGGL((prune_mean_kernel<KIND, DP, 8>), dim3((unsigned)(2 * wg)), dim3(1024), 0, s, a);
+  else hipLaunchKernelGGL((prune_mean_kernel<KIND, DP, 4>), dim3((unsigned)wg), dim3(1024), 0, s, a);
+}
+#endif
+
 template <int KIND, bool PRUNE>
 hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) {
   dim3 g((unsigned)grid), b(1024);
@@ -558,8 +850,23 @@ hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) 
 #endif
 // one translation unit holds either the plain instantiations or the PRUNE ones (tgp_kernels_sweep_prune_k*.hip)
 #ifdef TGP_SWEEP_PRUNE_TU
-hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid) {
-  return launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
+// `a.prune`'s header is zero.  Models of one row block: the single launch.  Otherwise means, list, survivors, fold -- in
+// stream order, no host synchronisation; what depends on the number of survivors is decided on the device.
+hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid, const PruneLaunch& pl) {
+  if (a.m.Npad / DBM <= 1) return launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
+  switch (a.m.dp) {
+    case 2: launch_prune_mean<TGP_SWEEP_KIND, 2>(s, a, grid, pl.mean_waves); break;
+    case 4: launch_prune_mean<TGP_SWEEP_KIND, 4>(s, a, grid, pl.mean_waves); break;
+    case 6: launch_prune_mean<TGP_SWEEP_KIND, 6>(s, a, grid, pl.mean_waves); break;
+    case 8: launch_prune_mean<TGP_SWEEP_KIND, 8>(s, a, grid, pl.mean_waves); break;
+    case 16: launch_prune_mean<TGP_SWEEP_KIND, 16>(s, a, grid, pl.mean_waves); break;
+    default: return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(prune_list_kernel, dim3(1), dim3(1024), 0, s, a, pl, (int)grid);
+  hipError_t e = launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
+  if (e != hipSuccess) return e;
+  if (pl.max_survivors > 0) hipLaunchKernelGGL(prune_fold_kernel, dim3((unsigned)pl.max_survivors), dim3(1024), 0, s, a);
+  return hipGetLastError();
 }
 #else
 hipError_t TGP_CAT(launch_sweep_dma_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid) {

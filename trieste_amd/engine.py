@@ -585,6 +585,21 @@ def prune_screened(eng: "GPEngine"):
     return s.value
 
 
+def set_prune_split(eng: "GPEngine", max_survivors: int = -1, max_groups: int = 0):
+    """The split regime of the pruned EI sweep (tgp_set_prune_split): blocks that survive the mean screen are cut into
+    ranges of row blocks when at most ``max_survivors`` survive (-1: the derived cap, 0: never), into at most
+    ``max_groups`` ranges each (0: up to the row blocks).  Same bits either way: a test and A/B aid."""
+    eng._chk(eng._lib.tgp_set_prune_split(eng._h, int(max_survivors), int(max_groups)))
+
+
+def prune_split(eng: "GPEngine"):
+    """(survivors of the mean screen, split work items) of ``eng``'s most recent arg-max (tgp_get_prune_split); items is 0
+    when the survivors ran whole.  Synchronises the engine's stream."""
+    s, i = C.c_int64(), C.c_int64()
+    eng._chk(eng._lib.tgp_get_prune_split(eng._h, C.byref(s), C.byref(i)))
+    return s.value, i.value
+
+
 class Trajectory:
     """B decoupled trajectories sharing one RFF basis (tgp_traj_*)."""
 
