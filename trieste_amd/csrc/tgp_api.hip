@@ -21,29 +21,6 @@
 
 #include "tgp_host.hpp"
 
-namespace tgp {
-hipError_t launch_sweep_kind0(hipStream_t, const SweepArgs&, bool, int64_t);
-hipError_t launch_sweep_kind1(hipStream_t, const SweepArgs&, bool, int64_t);
-hipError_t launch_sweep_kind2(hipStream_t, const SweepArgs&, bool, int64_t);
-hipError_t launch_sweep_kind3(hipStream_t, const SweepArgs&, bool, int64_t);
-hipError_t launch_sweep_dma_kind0(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_dma_kind1(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_dma_kind2(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_dma_kind3(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_prune_kind0(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
-hipError_t launch_sweep_prune_kind1(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
-hipError_t launch_sweep_prune_kind2(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
-hipError_t launch_sweep_prune_kind3(hipStream_t, const SweepArgs&, int64_t, const PruneLaunch&);
-hipError_t launch_joint_kind0(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_joint_kind1(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_joint_kind2(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_joint_kind3(hipStream_t, const SweepArgs&, int64_t);
-hipError_t launch_sweep_i8_kind0(hipStream_t, const SweepArgs&, int64_t, int);
-hipError_t launch_sweep_i8_kind1(hipStream_t, const SweepArgs&, int64_t, int);
-hipError_t launch_sweep_i8_kind2(hipStream_t, const SweepArgs&, int64_t, int);
-hipError_t launch_sweep_i8_kind3(hipStream_t, const SweepArgs&, int64_t, int);
-}  // namespace tgp
-
 using namespace tgp;
 
 namespace {
@@ -299,41 +276,32 @@ int64_t sweep_blocks(tgp_handle h, const SweepArgs& a, bool joint) {
   return sweep_grid(a, joint);
 }
 
-// row-group split of the f64 sweep: groups of row blocks of roughly equal triangular work
-bool plan_split(SweepArgs& am, int nb, int g) {
-  const int total = nb * (nb + 1) / 2;
-  am.split_ib[0] = 0;
-  int ib = 0;
-  for (int k = 1; k < g; ++k) {
-    while (ib < nb && ib * (ib + 1) / 2 < (int64_t)total * k / g) ++ib;
-    am.split_ib[k] = std::max(ib, am.split_ib[k - 1] + 1);
+// The events tgp_last_kernel_ms reads, around one sweep's launches: ev0 now; ev1 and the bookkeeping at stop() or, failing
+// that, when the scope ends (last_ms is resolved lazily from the two events).
+struct TimedLaunch {
+  tgp_handle h;
+  explicit TimedLaunch(tgp_handle handle) : h(handle) { (void)hipEventRecord(h->ev0, h->stream); }
+  TimedLaunch(const TimedLaunch&) = delete;
+  ~TimedLaunch() { stop(); }
+  void stop() {
+    if (!h) return;
+    (void)hipEventRecord(h->ev1, h->stream);
+    h->last_launches = 1;
+    h->last_ms = -1.0;
+    h = nullptr;
   }
-  am.split_ib[g] = nb;
-  bool ok = true;
-  for (int k = 0; k < g; ++k) ok = ok && am.split_ib[k] < am.split_ib[k + 1];
-  return ok;
-}
+};
 
-hipError_t launch_sweep_kind(tgp_handle h, const SweepArgs& a0, bool joint, int64_t wgrid) {
-  const SweepArgs* ap = &a0;
-  SweepArgs aw;
-  if (a0.m.dp > MAX_D) {  // wide inputs: the candidate coordinates of each workgroup's block go to device scratch, not LDS
-    if (hipError_t e = h->s_xqw.reserve((size_t)wgrid * (size_t)a0.m.dp * SW_BN * sizeof(double))) return e;
-    aw = a0;
-    aw.xqw = h->s_xqw.as<double>();
-    ap = &aw;
+hipError_t launch_sweep_kind(tgp_handle h, SweepArgs a, bool joint, int64_t wgrid) {
+  if (a.m.dp > MAX_D) {  // wide inputs: the candidate coordinates of each workgroup's block go to device scratch, not LDS
+    if (hipError_t e = h->s_xqw.reserve((size_t)wgrid * (size_t)a.m.dp * SW_BN * sizeof(double))) return e;
+    a.xqw = h->s_xqw.as<double>();
   }
-  const SweepArgs& a = *ap;
-  switch (h->kind) {
-    case TGP_RBF: return launch_sweep_kind0(h->stream, a, joint, wgrid);
-    case TGP_MATERN12: return launch_sweep_kind1(h->stream, a, joint, wgrid);
-    case TGP_MATERN32: return launch_sweep_kind2(h->stream, a, joint, wgrid);
-    default: return launch_sweep_kind3(h->stream, a, joint, wgrid);
-  }
+  return by_kind(launch_sweep_kinds, h->kind)(h->stream, a, joint, wgrid);
 }
 
 // split-precision sweep: digit planes of W (once per factorisation), 64-candidate blocks, 4 B / entry K* slabs
-hipError_t launch_sweep_i8_timed(tgp_handle h, SweepArgs& am) {
+hipError_t launch_sweep_i8_timed(tgp_handle h, SweepArgs am) {
   const int64_t Npad = am.m.Npad;
   hipError_t e;
   const int planes = h->precision == TGP_PREC_I8X5 ? 5 : 4;
@@ -367,17 +335,8 @@ hipError_t launch_sweep_i8_timed(tgp_handle h, SweepArgs& am) {
     am.rep_ub = nullptr;
     am.canary_rec = nullptr;
     am.adv_rec = nullptr;
-    (void)hipEventRecord(h->ev0, h->stream);
-    switch (h->kind) {
-      case TGP_RBF: e = launch_sweep_i8_kind0(h->stream, am, wgrid, planes); break;
-      case TGP_MATERN12: e = launch_sweep_i8_kind1(h->stream, am, wgrid, planes); break;
-      case TGP_MATERN32: e = launch_sweep_i8_kind2(h->stream, am, wgrid, planes); break;
-      default: e = launch_sweep_i8_kind3(h->stream, am, wgrid, planes); break;
-    }
-    (void)hipEventRecord(h->ev1, h->stream);
-    h->last_launches = 1;
-    h->last_ms = -1.0;
-    return e;
+    TimedLaunch timed(h);
+    return by_kind(launch_sweep_i8_kinds, h->kind)(h->stream, am, wgrid, planes);
   }
   // ---- with the a-posteriori repair (TGP_PREC_AUTO) -------------------------------------------------------------
   //  1 int8 sweep: values, per-candidate intervals (rep_ub; +inf = outside the parity tolerance), block winners = the
@@ -392,15 +351,7 @@ hipError_t launch_sweep_i8_timed(tgp_handle h, SweepArgs& am) {
   // one row block per group where there are at most 16: a handful of recomputed candidates is ONE candidate block, and
   // its latency is the heaviest group's walk (N = 4096: the last row block alone is 12 % of the triangle, 0.9 ms)
   int g = std::min(16, nb);
-  if (g == nb) {
-    for (int k = 0; k <= nb; ++k) b.split_ib[k] = k;
-  } else {
-    while (g > 1 && !plan_split(b, nb, g)) --g;  // (not every group count leaves every group a row block)
-  }
-  if (g == 1) {
-    b.split_ib[0] = 0;
-    b.split_ib[1] = nb;
-  }
+  while (!plan_row_split(b.split_ib, nb, g, true)) --g;  // (not every group count leaves every group a row block; one does)
   const int64_t cap = M + I8_ADV_GROUPS;   // the repair list: at most every candidate + the adversarial picks
   const int64_t cap_blocks = (cap + SW_BN - 1) / SW_BN;
   int64_t fgrid = cap_blocks * g;
@@ -473,21 +424,14 @@ hipError_t launch_sweep_i8_timed(tgp_handle h, SweepArgs& am) {
   // K_SIGMA = 8 standard deviations of the error model (tools/ozaki_tight.py: observed / model rms = 0.95 ... 0.97,
   // max over 2048 candidates 3.5); dropped digit pairs: 3 at weight 2^-32 (four planes), 4 at 2^-40 (five)
   am.rep_scale = h->auto_sigma * 2.0 * (planes == 4 ? std::exp2(-32.8) : std::exp2(-40.6)) * (I8_TIGHT * v);
-  double* user_acq = am.acq_out;
   double* ublk_val = am.blk_val;
   int64_t* ublk_idx = am.blk_idx;
   if (am.acq_kind >= 0 && !am.acq_out) am.acq_out = vals;
   am.kcache = h->s_kcache.as<double>();
-  (void)hipEventRecord(h->ev0, h->stream);
+  TimedLaunch timed(h);
   launch_repair_begin(h->stream, stats, M, (int64_t)h->auto_epoch, h->canary_epoch != h->auto_epoch);
   h->canary_epoch = h->auto_epoch;
-  switch (h->kind) {
-    case TGP_RBF: e = launch_sweep_i8_kind0(h->stream, am, wgrid, planes); break;
-    case TGP_MATERN12: e = launch_sweep_i8_kind1(h->stream, am, wgrid, planes); break;
-    case TGP_MATERN32: e = launch_sweep_i8_kind2(h->stream, am, wgrid, planes); break;
-    default: e = launch_sweep_i8_kind3(h->stream, am, wgrid, planes); break;
-  }
-  if (e != hipSuccess) return e;
+  if ((e = by_kind(launch_sweep_i8_kinds, h->kind)(h->stream, am, wgrid, planes)) != hipSuccess) return e;
   if (ublk_val) launch_argmax_final(h->stream, ublk_val, ublk_idx, blocks, Lslot, (int64_t*)(Lslot + 1));
   launch_repair_flag(h->stream, ub, M, ublk_val ? Lslot : nullptr, list, stats, can_off);
   launch_repair_adv(h->stream, adv_rec, blocks, list, stats, adv_sel);
@@ -527,20 +471,16 @@ hipError_t launch_sweep_i8_timed(tgp_handle h, SweepArgs& am) {
   launch_repair_scatter(h->stream, list, stats, cap, b.mean_out, am.var_out ? b.var_out : nullptr, b.acq_out, am.mean_out,
                         am.var_out, am.acq_out, ub, ublk_val ? Lslot : nullptr);
   if (ublk_val) launch_values_argmax(h->stream, am.acq_out, M, am.index_base, ublk_val, ublk_idx, blocks);
-  (void)hipEventRecord(h->ev1, h->stream);
-  e = hipMemcpyAsync(h->rep_host, stats, RS_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream);
-  am.acq_out = user_acq;
-  h->last_launches = 1;
-  h->last_ms = -1.0;
-  return e;
+  timed.stop();   // (in front of the report's copy)
+  return hipMemcpyAsync(h->rep_host, stats, RS_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream);
 }
 
-hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
+// (`a` by value: the scratch pointers and the split filled in here are this launch's own; the caller's arguments stay as they are)
+hipError_t launch_sweep_timed(tgp_handle h, SweepArgs a, bool joint) {
   const int64_t grid = sweep_grid(a, joint);
   if (grid <= 0) return hipSuccess;
   hipError_t e;
-  SweepArgs& am = const_cast<SweepArgs&>(a);
-  am.split_g = 0;
+  a.split_g = 0;
   if (!joint) {
     e = resolve_precision(h);
     h->auto_pinned = false;
@@ -548,7 +488,7 @@ hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
     // the digit planes, row scales and training-row tiles are built from THIS handle's factorisation (and cached per its
     // data_version): a sweep over another handle's model -- the repulsion twin of the entropy tails -- runs in float64
     const bool own_model = a.m.alpha == h->d_alpha.as<double>() && a.m.Npad == h->Npad;
-    if (h->precision != TGP_PREC_F64 && own_model) return launch_sweep_i8_timed(h, am);
+    if (h->precision != TGP_PREC_F64 && own_model) return launch_sweep_i8_timed(h, a);
   }
   if (joint && a.m.dp <= 16 && !(h->variant & VARIANT_JOINT_V1)) {
     // contiguously packed 128 x 256 tiles, Gram phase out of LDS (tgp_kernels_joint.inc)
@@ -559,21 +499,12 @@ hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
     hipError_t ea = h->s_kcache.reserve(slab);
     if (ea == hipSuccess) ea = h->s_aslab.reserve(slab);
     if (ea != hipSuccess) return ea;
-    am.kcache = h->s_kcache.as<double>();
-    am.aslab = h->s_aslab.as<double>();
+    a.kcache = h->s_kcache.as<double>();
+    a.aslab = h->s_aslab.as<double>();
     // (candidate blocks stay dealt, i, i + #WG, ...: drawn from a counter as in the int8 sweep the draw itself gains 0.5 % at
     // C4's 10 000 blocks, but the kernel compiled with it runs 1.7 % slower in either mode -- profiles/r06_joint_dynblocks.txt)
-    (void)hipEventRecord(h->ev0, h->stream);
-    switch (h->kind) {
-      case TGP_RBF: e = launch_joint_kind0(h->stream, a, wg); break;
-      case TGP_MATERN12: e = launch_joint_kind1(h->stream, a, wg); break;
-      case TGP_MATERN32: e = launch_joint_kind2(h->stream, a, wg); break;
-      default: e = launch_joint_kind3(h->stream, a, wg); break;
-    }
-    (void)hipEventRecord(h->ev1, h->stream);
-    h->last_launches = 1;
-    h->last_ms = -1.0;
-    return e;
+    TimedLaunch timed(h);
+    return by_kind(launch_joint_kinds, h->kind)(h->stream, a, wg);
   }
   const bool want_split = (h->variant & VARIANT_FORCE_SPLIT) ||
                           (grid < 4 * (int64_t)h->num_cu && !(h->variant & VARIANT_NO_SPLIT));
@@ -587,23 +518,20 @@ hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
     // (round 6: with as many groups as row blocks the equal-work boundaries leave a group empty -- nb = 4 and nb = 8, i.e.
     // N <= 1024 and N <= 2048, never split at all and EGO's 8000-candidate sweep ran on 125 of 256 compute units: 2.2 ms at
     // N = 2048 for 0.5 ms of arithmetic; take the largest group count that works)
-    while (g > 1 && !plan_split(am, nb, g)) --g;
+    while (g > 1 && !plan_row_split(a.split_ib, nb, g, false)) --g;
     if (g > 1) {
-      const bool ok = true;
-      if (ok) {
-        am.split_g = g;
-        hipError_t ep = h->s_part.reserve((size_t)grid * g * 256 * sizeof(double));
-        if (ep != hipSuccess) return ep;
-        am.part = h->s_part.as<double>();
-      }
+      a.split_g = g;
+      hipError_t ep = h->s_part.reserve((size_t)grid * g * 256 * sizeof(double));
+      if (ep != hipSuccess) return ep;
+      a.part = h->s_part.as<double>();
     }
   }
-  if (!joint && am.split_g <= 1 && a.m.dp <= 16 && !(h->variant & VARIANT_REG_STAGING)) {
+  if (!joint && a.split_g <= 1 && a.m.dp <= 16 && !(h->variant & VARIANT_REG_STAGING)) {
     // fused plain launch: LDS-DMA staging, three A stages (tgp_kernels_sweep_dma.inc); same results bit for bit
     const int64_t wg = grid < h->num_cu ? grid : h->num_cu;
     hipError_t ea = h->s_kcache.reserve((size_t)wg * (size_t)a.m.Npad * SW_BN * sizeof(double));
     if (ea != hipSuccess) return ea;
-    am.kcache = h->s_kcache.as<double>();
+    a.kcache = h->s_kcache.as<double>();
     // only the winner is consumed and EI grows with the variance: candidate blocks whose EI bound cannot win are given up
     // at a row-block boundary (PRUNE instantiation; the same winner bit for bit)
     const bool prune = a.acq_kind == TGP_ACQ_EI && a.blk_val && !a.acq_out && !a.mean_out && !a.var_out &&
@@ -620,54 +548,34 @@ hipError_t launch_sweep_timed(tgp_handle h, const SweepArgs& a, bool joint) {
         pl.max_groups = h->prune_max_groups;
         static const bool mean4 = getenv("TGP_PRUNE_MEAN_WAVES4") != nullptr;  // A/B aid: phase 1 at four waves per SIMD
         pl.mean_waves = mean4 ? 4 : 8;
-        words = prune_dump_word(grid) + (size_t)pl.max_survivors * nb * PRUNE_DUMP_BLOCK;
+        words = PruneView::words(grid, pl.max_survivors, nb);
       }
       ea = h->s_prune.reserve(words * sizeof(unsigned long long));
       if (ea != hipSuccess) return ea;
-      am.prune = h->s_prune.as<unsigned long long>();
-      am.prune_flags = ((h->variant & VARIANT_PRUNE_NO_SCREEN) ? 1 : 0) | ((h->variant & VARIANT_PRUNE_STATIC_BLOCKS) ? 2 : 0);
+      a.prune = h->s_prune.as<unsigned long long>();
+      a.prune_flags = ((h->variant & VARIANT_PRUNE_NO_SCREEN) ? 1 : 0) | ((h->variant & VARIANT_PRUNE_STATIC_BLOCKS) ? 2 : 0);
     }
-    (void)hipEventRecord(h->ev0, h->stream);
-    if (prune) {
-      e = hipMemsetAsync(am.prune, 0, PRUNE_HDR_WORDS * sizeof(unsigned long long), h->stream);
-      if (e != hipSuccess) return e;
-      h->prune_blocks = grid;
-      switch (h->kind) {
-        case TGP_RBF: e = launch_sweep_prune_kind0(h->stream, a, wg, pl); break;
-        case TGP_MATERN12: e = launch_sweep_prune_kind1(h->stream, a, wg, pl); break;
-        case TGP_MATERN32: e = launch_sweep_prune_kind2(h->stream, a, wg, pl); break;
-        default: e = launch_sweep_prune_kind3(h->stream, a, wg, pl); break;
-      }
-    } else {
-      switch (h->kind) {
-        case TGP_RBF: e = launch_sweep_dma_kind0(h->stream, a, wg); break;
-        case TGP_MATERN12: e = launch_sweep_dma_kind1(h->stream, a, wg); break;
-        case TGP_MATERN32: e = launch_sweep_dma_kind2(h->stream, a, wg); break;
-        default: e = launch_sweep_dma_kind3(h->stream, a, wg); break;
-      }
-    }
-    (void)hipEventRecord(h->ev1, h->stream);
-    h->last_launches = 1;
-    h->last_ms = -1.0;
-    return e;
+    TimedLaunch timed(h);
+    if (!prune) return by_kind(launch_sweep_dma_kinds, h->kind)(h->stream, a, wg);
+    e = hipMemsetAsync(a.prune, 0, PRUNE_HDR_WORDS * sizeof(unsigned long long), h->stream);
+    if (e != hipSuccess) return e;
+    h->prune_blocks = grid;
+    return by_kind(launch_sweep_prune_kinds, h->kind)(h->stream, a, wg, pl);
   }
   // persistent: one workgroup per CU, each with a private K* slab (and a C slab in joint mode)
-  int64_t wgrid = grid * std::max(1, am.split_g);
+  int64_t wgrid = grid * std::max(1, a.split_g);
   wgrid = wgrid < h->num_cu ? wgrid : h->num_cu;
   hipError_t ea = h->s_kcache.reserve((size_t)wgrid * (size_t)a.m.Npad * SW_BN * sizeof(double));
   if (ea != hipSuccess) return ea;
-  am.kcache = h->s_kcache.as<double>();
+  a.kcache = h->s_kcache.as<double>();
   if (joint) {
     ea = h->s_aslab.reserve((size_t)wgrid * (size_t)a.m.Npad * SW_BN * sizeof(double));
     if (ea != hipSuccess) return ea;
-    am.aslab = h->s_aslab.as<double>();
+    a.aslab = h->s_aslab.as<double>();
   }
-  (void)hipEventRecord(h->ev0, h->stream);
+  TimedLaunch timed(h);
   e = launch_sweep_kind(h, a, joint, wgrid);
-  if (e == hipSuccess && am.split_g > 1) launch_sweep_combine(h->stream, a, grid);
-  (void)hipEventRecord(h->ev1, h->stream);
-  h->last_launches = 1;
-  h->last_ms = -1.0;  // resolved lazily in tgp_last_kernel_ms
+  if (e == hipSuccess && a.split_g > 1) launch_sweep_combine(h->stream, a, grid);
   return e;
 }
 
@@ -3099,11 +3007,10 @@ int tgp_traj_eval(tgp_traj t, const double* Xq, int64_t M, int per_traj_inputs, 
   double* dout;
   if (int rc = stage_in(h, h->s_in, Xq, nin, where, &dXq)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, out, (size_t)M * t->B, where, &dout)) return rc;
-  (void)hipEventRecord(h->ev0, h->stream);
-  launch_traj_eval(h->stream, traj_dev(t), dXq, M, per_traj_inputs, dout, nullptr, nullptr, 0);
-  (void)hipEventRecord(h->ev1, h->stream);
-  h->last_launches = 1;
-  h->last_ms = -1.0;
+  {
+    TimedLaunch timed(h);
+    launch_traj_eval(h->stream, traj_dev(t), dXq, M, per_traj_inputs, dout, nullptr, nullptr, 0);
+  }
   if (int rc = stage_out_finish(h, dout, out, (size_t)M * t->B, where)) return rc;
   if (int rc = sync(h)) return rc;
   HIPCHK(h, hipGetLastError());
@@ -3138,12 +3045,10 @@ static int enqueue_traj_argmin(tgp_traj t, const double* dXq, int64_t M, int64_t
   const int B = t->B;
   HIPCHK(h, h->s_blkv.reserve((size_t)grid * B * sizeof(double)));
   HIPCHK(h, h->s_blki.reserve((size_t)grid * B * sizeof(int64_t)));
-  (void)hipEventRecord(h->ev0, h->stream);
-  launch_traj_eval(h->stream, traj_dev(t), dXq, M, 0, nullptr, h->s_blkv.as<double>(),
-                   h->s_blki.as<int64_t>(), index_base);
-  (void)hipEventRecord(h->ev1, h->stream);
-  h->last_launches = 1;
-  h->last_ms = -1.0;
+  {
+    TimedLaunch timed(h);
+    launch_traj_eval(h->stream, traj_dev(t), dXq, M, 0, nullptr, h->s_blkv.as<double>(), h->s_blki.as<int64_t>(), index_base);
+  }
   launch_argmin_final_multi(h->stream, h->s_blkv.as<double>(), h->s_blki.as<int64_t>(), grid, B, fv, fi);
   return TGP_OK;
 }
@@ -3192,7 +3097,8 @@ int tgp_stream_synchronize(tgp_handle h) {
   return TGP_OK;
 }
 
-static int read_prune_words(tgp_handle h, unsigned long long (&w)[4]) {
+// the header words of the last pruned arg-max up to the range boundaries (tgp_internal.hpp PRUNE_W_*); zeros when none ran
+static int read_prune_words(tgp_handle h, unsigned long long (&w)[PRUNE_W_IB]) {
   for (auto& x : w) x = 0;
   if (h->prune_blocks > 0) {
     if (int rc = set_device(h)) return rc;
@@ -3204,11 +3110,11 @@ static int read_prune_words(tgp_handle h, unsigned long long (&w)[4]) {
 
 int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int64_t* row_blocks_skipped) {
   if (!h) return TGP_ERR_ARG;
-  unsigned long long w[4];
+  unsigned long long w[PRUNE_W_IB];
   if (int rc = read_prune_words(h, w)) return rc;
   if (blocks) *blocks = h->prune_blocks;
-  if (given_up) *given_up = (int64_t)w[1];
-  if (row_blocks_skipped) *row_blocks_skipped = (int64_t)w[2];
+  if (given_up) *given_up = (int64_t)w[PRUNE_W_GIVEN_UP];
+  if (row_blocks_skipped) *row_blocks_skipped = (int64_t)w[PRUNE_W_SKIPPED];
   return TGP_OK;
 }
 
@@ -3221,13 +3127,8 @@ int tgp_set_prune_split(tgp_handle h, int max_survivors, int max_groups) {
 
 int tgp_get_prune_split(tgp_handle h, int64_t* survivors, int64_t* items) {
   if (!h) return TGP_ERR_ARG;
-  unsigned long long w[8];
-  for (auto& x : w) x = 0;
-  if (h->prune_blocks > 0) {
-    if (int rc = set_device(h)) return rc;
-    HIPCHK(h, hipMemcpyAsync(w, h->s_prune.p, sizeof w, hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync(h)) return rc;
-  }
+  unsigned long long w[PRUNE_W_IB];
+  if (int rc = read_prune_words(h, w)) return rc;
   if (survivors) *survivors = (int64_t)w[PRUNE_W_SURVIVORS];
   if (items) *items = (int64_t)w[PRUNE_W_ITEMS];
   return TGP_OK;
@@ -3235,9 +3136,9 @@ int tgp_get_prune_split(tgp_handle h, int64_t* survivors, int64_t* items) {
 
 int tgp_get_prune_screened(tgp_handle h, int64_t* screened) {
   if (!h) return TGP_ERR_ARG;
-  unsigned long long w[4];
+  unsigned long long w[PRUNE_W_IB];
   if (int rc = read_prune_words(h, w)) return rc;
-  if (screened) *screened = (int64_t)w[3];
+  if (screened) *screened = (int64_t)w[PRUNE_W_SCREENED];
   return TGP_OK;
 }
 

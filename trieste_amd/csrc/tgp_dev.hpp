@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tgp_internal.hpp"  // SweepArgs (the sweep epilogue below)
+
 namespace tgp {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -330,6 +332,78 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
+}
+
+// ---- the epilogue of the float64 sweep family (sweep_kernel, sweep_dma_kernel, prune_fold_kernel, sweep_combine_kernel):
+// one body each, because the kernels promise each other the same bits -------------------------------------------------------
+// Column norms of a 16-wave 256 x 128 tile: wave (wm, wn) holds, per lane, the partial sums of squares of columns
+// wn 32 + (lane & 15) and + 16 over its rows.  The four lane groups are summed, then wave row wm leaves its 128 sums in
+// area [4][128]; after a barrier colnorm_read adds the four wave rows, bracketed (a + b) + (c + d).
+// (The parameter order (wn, wm) and colnorm_read's pointer form are what leaves the plain instantiations of sweep_dma_kernel
+// their machine code.  sweep_kernel writes the two out: there every form tried as a call reordered its code.)
+__device__ __forceinline__ void colnorm_reduce(double* area, double s0, double s1, int wn, int wm, int lane) {
+  s0 += __shfl_xor(s0, 16, 64);
+  s0 += __shfl_xor(s0, 32, 64);
+  s1 += __shfl_xor(s1, 16, 64);
+  s1 += __shfl_xor(s1, 32, 64);
+  if (lane < 16) {
+    area[wm * 128 + wn * 32 + lane] = s0;
+    area[wm * 128 + wn * 32 + 16 + lane] = s1;
+  }
+}
+__device__ __forceinline__ double colnorm_read(const double* col) {   // col = area + column
+  return (col[0] + col[128]) + (col[256] + col[384]);
+}
+
+// column col's mean from the eight row groups' partial dot products k* . alpha in mred [8][128]
+__device__ __forceinline__ double mean_reduce(const SweepArgs& a, const double* mred, int col) {
+  double m = 0.0;
+#pragma unroll
+  for (int g = 0; g < 8; ++g) m += mred[g * 128 + col];
+  return m + a.m.mean_const;
+}
+
+// Candidate cj's tail on its mean and clipped variance: the outputs that were asked for, the acquisition value; (val, gidx)
+// take the value unless it is NaN (NaN never wins).
+__device__ __forceinline__ void sweep_tail(const SweepArgs& a, int64_t cj, double mean, double var, double& val,
+                                           int64_t& gidx) {
+  if (a.mean_out) a.mean_out[cj] = mean;
+  if (a.var_out) a.var_out[cj] = var;
+  if (a.acq_kind >= 0) {
+    const double v = acq_tail(a.acq_kind, a.acq_param, mean, var, a.m.noise);
+    if (a.acq_out) a.acq_out[cj] = v;
+    if (!(v != v)) {
+      val = v;
+      gidx = a.index_base + cj;
+    }
+  }
+}
+
+// The winner of a candidate block whose 128 candidates sit on threads 0 .. 127: (larger value, smaller index) over the two
+// waves (w: the caller's wave index) through bvs / bis [2], written to blk_val / blk_idx [blk].  Contains a barrier: every
+// thread of the workgroup calls it.  Thread 0 returns the winning value (every other thread -inf).
+__device__ __forceinline__ double block_winner(const SweepArgs& a, int64_t blk, double val, int64_t gidx, double* bvs,
+                                               int64_t* bis, int tid, int w) {
+  if (tid < 128) {
+    wave_argmax(val, gidx);
+    if ((tid & 63) == 0) {
+      bvs[w] = val;
+      bis[w] = gidx;
+    }
+  }
+  __syncthreads();
+  double v0 = -INFINITY;
+  if (tid == 0) {
+    v0 = bvs[0];
+    int64_t i0 = bis[0];
+    if (better(bvs[1], bis[1], v0, i0)) {
+      v0 = bvs[1];
+      i0 = bis[1];
+    }
+    a.blk_val[blk] = v0;
+    a.blk_idx[blk] = i0;
+  }
+  return v0;
 }
 
 // ---- Philox4x32-10 -------------------------------------------------------------------------

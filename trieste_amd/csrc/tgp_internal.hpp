@@ -91,24 +91,63 @@ struct SweepArgs {
                           // repair pass over the flagged candidates is enqueued without a host round trip)
   double* xqw;            // wide sweeps (dp > MAX_D): [grid][dp][128] per-workgroup scaled candidate coordinates (device
                           // scratch beside the K* slabs; the narrow instantiations keep them in LDS)
-  // the pruned EI arg-max (PRUNE instantiation of sweep_dma_kernel): [0] the best word: the bits of the largest of the
-  // finished block maxima and the blocks' seeds eta - mean (EI >= 0: unsigned order is value order), [1] candidate blocks
-  // given up, [2] row blocks behind the first that they did not compute, [3] blocks given up by the mean screen (they did
-  // not compute the first row block either), [4] the counter candidate blocks are drawn from; ALL ZERO at launch (memset
-  // before every launch: a stale best would be a wrong result)
-  // Models of more than one row block run in three phases and keep more behind the same pointer: words
-  // [PRUNE_W_SURVIVORS] S, [PRUNE_W_ITEMS] split work items (0: whole-block regime), [PRUNE_W_GROUPS] ranges per survivor,
-  // [PRUNE_W_IB ..] the range boundaries; from word PRUNE_HDR_WORDS on the blocks' bounds [nblk] (double), the survivor list
-  // [nblk] (int64), the means [nblk][128] (double) and, rounded up to 32 words, the accumulator dump
-  // [survivor][row block][32][1024] (double).  Only the header is cleared per launch: everything else is written before it is read.
-  unsigned long long* prune;
+  unsigned long long* prune;   // the pruned EI arg-max (PRUNE instantiation of sweep_dma_kernel): see PruneView
 };
-constexpr int PRUNE_W_SURVIVORS = 5, PRUNE_W_ITEMS = 6, PRUNE_W_GROUPS = 7, PRUNE_W_IB = 16, PRUNE_MAX_GROUPS = 64,
+// The buffer behind SweepArgs::prune.  Header words, ALL ZERO at launch (memset before every launch: a stale best would be a
+// wrong result):
+//   PRUNE_W_BEST      the best word: the bits of the largest of the finished block maxima and the blocks' seeds eta - mean
+//                     (EI >= 0: unsigned order is value order)
+//   PRUNE_W_GIVEN_UP  candidate blocks given up       PRUNE_W_SKIPPED  row blocks behind the first that they did not compute
+//   PRUNE_W_SCREENED  blocks given up by the mean screen (they did not compute the first row block either)
+//   PRUNE_W_DRAW      the counter candidate blocks are drawn from
+// Models of more than one row block run in three phases and keep more behind the same pointer:
+//   PRUNE_W_SURVIVORS S      PRUNE_W_ITEMS  split work items (0: whole-block regime)      PRUNE_W_GROUPS  ranges per survivor
+//   PRUNE_W_IB ..     the range boundaries
+// and from word PRUNE_HDR_WORDS on the areas of PruneView.  Only the header is cleared per launch: everything else is
+// written before it is read.
+constexpr int PRUNE_W_BEST = 0, PRUNE_W_GIVEN_UP = 1, PRUNE_W_SKIPPED = 2, PRUNE_W_SCREENED = 3, PRUNE_W_DRAW = 4,
+              PRUNE_W_SURVIVORS = 5, PRUNE_W_ITEMS = 6, PRUNE_W_GROUPS = 7, PRUNE_W_IB = 16, PRUNE_MAX_GROUPS = 64,
               PRUNE_HDR_WORDS = 128;
 constexpr size_t PRUNE_DUMP_BLOCK = 32 * 1024;                   // doubles per (survivor, row block): 256 KiB
 constexpr size_t PRUNE_DUMP_MAX_BYTES = (size_t)1 << 30;         // the dump area never exceeds this, nor the launch's K* slabs
-inline __host__ __device__ size_t prune_dump_word(int64_t nblk) {
-  return ((size_t)PRUNE_HDR_WORDS + (size_t)nblk * (2 + SW_BN) + 31) / 32 * 32;
+struct PruneView {   // the areas behind the header of a launch over nblk candidate blocks
+  unsigned long long* w;
+  int64_t nblk;
+  __host__ __device__ double* bounds() const { return (double*)(w + PRUNE_HDR_WORDS); }               // [nblk] blocks' bounds
+  __host__ __device__ int64_t* list() const { return (int64_t*)(w + PRUNE_HDR_WORDS + nblk); }        // [nblk] survivors
+  __host__ __device__ double* means() const { return (double*)(w + PRUNE_HDR_WORDS + 2 * nblk); }     // [nblk][128]
+  // the accumulator dump [survivor][row block of nb][32][1024], from a multiple of 32 words on
+  static __host__ __device__ size_t dump_word(int64_t nblk) {
+    return ((size_t)PRUNE_HDR_WORDS + (size_t)nblk * (2 + SW_BN) + 31) / 32 * 32;
+  }
+  __host__ __device__ double* dump(int64_t survivor, int ib, int nb) const {
+    return (double*)(w + dump_word(nblk)) + ((size_t)survivor * nb + ib) * PRUNE_DUMP_BLOCK;
+  }
+  static __host__ __device__ size_t words(int64_t nblk, int64_t survivors, int nb) {   // the whole buffer
+    return dump_word(nblk) + (size_t)survivors * nb * PRUNE_DUMP_BLOCK;
+  }
+};
+// Row blocks [0, nb) of W in g ranges [ib[k], ib[k + 1]) of roughly equal triangular work.  False when a range came out
+// empty: the caller takes a smaller g (g = 1 always works).  `singles`: g == nb means one row block per range; without it
+// the equal-work boundaries at g == nb leave a range empty (nb = 4 and 8) and the call fails like any other.
+template <typename T>
+inline __host__ __device__ bool plan_row_split(T* ib, int nb, int g, bool singles) {
+  if (singles && g == nb) {
+    for (int k = 0; k <= g; ++k) ib[k] = (T)k;
+    return true;
+  }
+  const int total = nb * (nb + 1) / 2;
+  ib[0] = 0;
+  int i = 0;
+  for (int k = 1; k < g; ++k) {
+    while (i < nb && i * (i + 1) / 2 < (int64_t)total * k / g) ++i;
+    const int prev = (int)ib[k - 1] + 1;
+    ib[k] = (T)(i > prev ? i : prev);
+  }
+  ib[g] = (T)nb;
+  bool ok = true;
+  for (int k = 0; k < g; ++k) ok = ok && ib[k] < ib[k + 1];
+  return ok;
 }
 // the three-phase launch of the pruned EI arg-max (tgp_kernels_sweep_dma.inc): the effective knobs of tgp_set_prune_split
 struct PruneLaunch {
@@ -162,6 +201,23 @@ void launch_axpby_vec(hipStream_t s, int64_t n, double a, const double* x, doubl
 
 // ---- sweep (tgp_kernels_sweep_*.hip) ----
 int64_t sweep_grid(const SweepArgs& a, bool joint);
+// A launcher family has one entry point per kernel kind, NAME0 .. NAME3 (one translation unit per kind); NAMEs is the family
+// as a table and by_kind picks a handle's entry: TGP_RBF, TGP_MATERN12, TGP_MATERN32 are 0, 1, 2 and anything else is kind 3.
+#define TGP_KIND_FAMILY(name, ...)                                                                                  \
+  hipError_t name##0(__VA_ARGS__);                                                                                  \
+  hipError_t name##1(__VA_ARGS__);                                                                                  \
+  hipError_t name##2(__VA_ARGS__);                                                                                  \
+  hipError_t name##3(__VA_ARGS__);                                                                                  \
+  inline constexpr hipError_t (*name##s[4])(__VA_ARGS__) = {name##0, name##1, name##2, name##3}
+TGP_KIND_FAMILY(launch_sweep_kind, hipStream_t, const SweepArgs&, bool joint, int64_t grid);
+TGP_KIND_FAMILY(launch_sweep_dma_kind, hipStream_t, const SweepArgs&, int64_t grid);
+TGP_KIND_FAMILY(launch_sweep_prune_kind, hipStream_t, const SweepArgs&, int64_t grid, const PruneLaunch&);
+TGP_KIND_FAMILY(launch_joint_kind, hipStream_t, const SweepArgs&, int64_t grid);
+TGP_KIND_FAMILY(launch_sweep_i8_kind, hipStream_t, const SweepArgs&, int64_t grid, int planes);
+template <typename F>
+inline F by_kind(F const (&family)[4], int kind) {
+  return family[kind >= 0 && kind < 3 ? kind : 3];
+}
 
 // ---- misc (tgp_kernels_misc.hip) ----
 void launch_predict_mean(hipStream_t s, const ModelDev& m, const double* Xq, int64_t M, double* mean);

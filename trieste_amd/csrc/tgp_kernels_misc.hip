@@ -146,7 +146,7 @@ void launch_predict_mean(hipStream_t s, const ModelDev& m, const double* Xq, int
 __global__ __launch_bounds__(128) void sweep_combine_kernel(SweepArgs a) {
   __shared__ double bvs[2];
   __shared__ int64_t bis[2];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t M = a.M_dev ? *a.M_dev : a.M;  // repair pass: the count of flagged candidates lives on the device
   const int64_t nblk = (M + 127) / 128;
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -160,36 +160,10 @@ __global__ __launch_bounds__(128) void sweep_combine_kernel(SweepArgs a) {
         m += pp[tid];
         sq += pp[128 + tid];
       }
-      const double mean = m + a.m.mean_const;
-      const double var = fmax(a.m.variance - sq, VAR_FLOOR);
-      if (a.mean_out) a.mean_out[cj] = mean;
-      if (a.var_out) a.var_out[cj] = var;
-      if (a.acq_kind >= 0) {
-        const double v = acq_tail(a.acq_kind, a.acq_param, mean, var, a.m.noise);
-        if (a.acq_out) a.acq_out[cj] = v;
-        if (!(v != v)) {
-          val = v;
-          gidx = a.index_base + cj;
-        }
-      }
+      sweep_tail(a, cj, m + a.m.mean_const, fmax(a.m.variance - sq, VAR_FLOOR), val, gidx);
     }
     if (a.blk_val) {
-      wave_argmax(val, gidx);
-      if (lane == 0) {
-        bvs[w] = val;
-        bis[w] = gidx;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        double v0 = bvs[0];
-        int64_t i0 = bis[0];
-        if (better(bvs[1], bis[1], v0, i0)) {
-          v0 = bvs[1];
-          i0 = bis[1];
-        }
-        a.blk_val[blk] = v0;
-        a.blk_idx[blk] = i0;
-      }
+      block_winner(a, blk, val, gidx, bvs, bis, tid, tid >> 6);
       __syncthreads();
     }
   }

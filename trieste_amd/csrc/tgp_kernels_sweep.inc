@@ -353,7 +353,7 @@ __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
     }
     // ---- reductions (LDS is free after the last barrier) ---------------------------------------
     mred[krg * 128 + kcol] = macc;
-    {
+    {  // (colnorm_reduce / colnorm_read of tgp_dev.hpp, written out: as calls they reorder this kernel's machine code)
       double s0 = ssq0, s1 = ssq1;
       s0 += __shfl_xor(s0, 16, 64);
       s0 += __shfl_xor(s0, 32, 64);
@@ -370,10 +370,9 @@ __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
         double m = 0.0;
 #pragma unroll
         for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
-        const double sq = (sred[tid] + sred[128 + tid]) + (sred[256 + tid] + sred[384 + tid]);
         double* pp = a.part + ((size_t)blk * ngrp + grp) * 256;
         pp[tid] = m;
-        pp[128 + tid] = sq;
+        pp[128 + tid] = (sred[tid] + sred[128 + tid]) + (sred[256 + tid] + sred[384 + tid]);
       }
       __syncthreads();  // scratch / xqs are rewritten by the next work item
       continue;
@@ -424,44 +423,12 @@ __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
     if (!JOINT && tid < 128) {
       const int64_t cj = blk * UBN + tid;
       if (cj < Mrun) {
-        double m = 0.0;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
-        const double mean = m + a.m.mean_const;
+        const double mean = mean_reduce(a, mred, tid);
         const double s = (sred[tid] + sred[128 + tid]) + (sred[256 + tid] + sred[384 + tid]);
-        const double var = fmax(variance - s, VAR_FLOOR);
-        if (a.mean_out) a.mean_out[cj] = mean;
-        if (a.var_out) a.var_out[cj] = var;
-        if (a.acq_kind >= 0) {
-          const double v = acq_tail(a.acq_kind, a.acq_param, mean, var, a.m.noise);
-          if (a.acq_out) a.acq_out[cj] = v;
-          if (!(v != v)) {
-            val = v;
-            gidx = a.index_base + cj;
-          }
-        }
+        sweep_tail(a, cj, mean, fmax(variance - s, VAR_FLOOR), val, gidx);
       }
     }
-    if (a.blk_val) {
-      if (tid < 128) {
-        wave_argmax(val, gidx);
-        if (lane == 0) {
-          bvs[w] = val;
-          bis[w] = gidx;
-        }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        double v0 = bvs[0];
-        int64_t i0 = bis[0];
-        if (better(bvs[1], bis[1], v0, i0)) {
-          v0 = bvs[1];
-          i0 = bis[1];
-        }
-        a.blk_val[blk] = v0;
-        a.blk_idx[blk] = i0;
-      }
-    }
+    if (a.blk_val) block_winner(a, blk, val, gidx, bvs, bis, tid, w);
     __syncthreads();  // scratch / xqs are rewritten by the next block
   }
 }

@@ -168,6 +168,26 @@ __device__ __forceinline__ void prune_generate(const SweepArgs& a, const double*
   }
 }
 
+// coordinate c of column j of block blk, scaled by its lengthscale, into xqs [DP][128] (c-major); columns past M repeat
+// candidate 0.  (One entry, the caller keeps the loop `e = tid, tid + 1024, ..; j = e / DP, c = e % DP`: with the loop or the
+// division in here the plain instantiations of sweep_dma_kernel compile to other machine code.)
+__device__ __forceinline__ void scale_entry(double* xqs, const double* Xq, int64_t M, int d, const double* ls, int64_t blk,
+                                            int j, int c) {
+  const int64_t cand = blk * DBN + j;
+  const int64_t src = cand < M ? cand : 0;
+  xqs[c * DBN + j] = (c < d) ? Xq[src * d + c] / as_const(ls)[c] : 0.0;
+}
+
+// PRUNE, the seed (threads 0 .. 127, column `valid` with mean pm): the block's largest eta - mean over its valid columns
+// raises the best word (a NaN mean posts nothing)
+__device__ __forceinline__ void post_seed(const SweepArgs& a, bool valid, double pm, int lane) {
+  double seed = valid ? a.acq_param - pm : 0.0;
+  if (!(seed > 0.0)) seed = 0.0;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) seed = fmax(seed, __shfl_xor(seed, o, 64));
+  if (lane == 0 && seed > 0.0) atomicMax(a.prune + PRUNE_W_BEST, (unsigned long long)__double_as_longlong(seed));
+}
+
 template <int KIND, int DP, bool PRUNE>
 __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   static_assert(!PRUNE || TGP_DMA_DEFER, "the checkpoint sits behind the deferred MFMAs");
@@ -203,6 +223,8 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   double* const kc = a.kcache + (size_t)blockIdx.x * (size_t)Npad * DBN;
   const int64_t nblk = (a.M + DBN - 1) / DBN;
   const int T = nb * (nb + 1) / 2 * DKSTEPS;
+  // PRUNE only; a view per use: a named one, captured by the lambdas below, costs this instantiation 16 bytes of scratch
+  auto pv = [&]() { return PruneView{a.prune, nblk}; };
 
   // PRUNE, phase 2 (nb > 1): the blocks are the entries of the survivor list.  Split regime (items > 0): this workgroup
   // is work item blockIdx.x = (survivor, range), row blocks [ib_lo, ib_hi) of the one block, and nothing else.
@@ -213,7 +235,7 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   if constexpr (PRUNE) {
     if (listed) {
       const unsigned long long* hdr = a.prune;
-      const int64_t* list = (const int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk);
+      const int64_t* list = pv().list();
       nsurv = (int64_t)hdr[PRUNE_W_SURVIVORS];
       const int items = (int)hdr[PRUNE_W_ITEMS], groups = (int)hdr[PRUNE_W_GROUPS];
       split = items > 0;
@@ -245,23 +267,18 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
         pos = (listed ? li : blk) + gridDim.x;
         __syncthreads();
       } else {
-        if (tid == 0) *pdraw = (int64_t)gridDim.x + (int64_t)atomicAdd(a.prune + 4, 1ull);
+        if (tid == 0) *pdraw = (int64_t)gridDim.x + (int64_t)atomicAdd(a.prune + PRUNE_W_DRAW, 1ull);
         __syncthreads();
         pos = *pdraw;   // (rewritten at the next draw, behind this block's barriers)
       }
       if (listed) {
         li = pos;
-        blk_next = pos < nsurv ? ((const int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk))[pos] : nblk;
+        blk_next = pos < nsurv ? pv().list()[pos] : nblk;
       } else {
         blk_next = pos;
       }
     };
-    for (int e = tid; e < DBN * DP; e += 1024) {  // scale the block's candidates once (c-major)
-      const int j = e / DP, c = e % DP;
-      const int64_t cand = blk * DBN + j;
-      const int64_t src = cand < a.M ? cand : 0;
-      xqs[c * DBN + j] = (c < d) ? a.Xq[src * d + c] / as_const(a.m.ls)[c] : 0.0;
-    }
+    for (int e = tid; e < DBN * DP; e += 1024) scale_entry(xqs, a.Xq, a.M, d, a.m.ls, blk, e / DP, e % DP);   // once per block
     v4d acc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -274,27 +291,16 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
     // a model of one row block generates its K* here, into the mean and the slab at once (there is no screen to wait for)
     if constexpr (PRUNE) {
       if (listed) {   // (read behind the barriers that follow the slab generation)
-        if (tid < 128) pmean[tid] = ((const double*)(a.prune + PRUNE_HDR_WORDS + 2 * nblk))[blk * DBN + tid];
+        if (tid < 128) pmean[tid] = pv().means()[blk * DBN + tid];
       }
     }
     if constexpr (PRUNE) if (!listed) {   // (one row block)
       prune_generate<KIND, DP, GEN_MEAN | GEN_SLAB>(a, xqs, kcol, krg, nb * DKSTEPS, kc, variance, macc);
       mred[krg * 128 + kcol] = macc;   // (no DMA is in flight: A stage 0 is free)
       __syncthreads();
-      const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN);
       if (tid < 128) {
-        double m = 0.0;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
-        const double pm = m + a.m.mean_const;
-        pmean[tid] = pm;
-        if (screen) {   // the seed: the block's largest eta - mean over valid columns (a NaN mean posts nothing)
-          double seed = blk * DBN + tid < a.M ? a.acq_param - pm : 0.0;
-          if (!(seed > 0.0)) seed = 0.0;
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) seed = fmax(seed, __shfl_xor(seed, o, 64));
-          if (lane == 0 && seed > 0.0) atomicMax(a.prune, (unsigned long long)__double_as_longlong(seed));
-        }
+        const double pm = pmean[tid] = mean_reduce(a, mred, tid);
+        if (!(a.prune_flags & PRUNE_NO_SCREEN)) post_seed(a, blk * DBN + tid < a.M, pm, lane);
       }
       __syncthreads();   // mred is A stage 0 again
     }
@@ -372,23 +378,15 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
     // PRUNE checkpoint (all accumulators have just been folded and cleared): true when every candidate's EI bound lies
     // below the best finished block maximum by more than the tail's own resolution -- one decision per workgroup
     auto cannot_win = [&]() -> bool {
-      double s0 = ssq0, s1 = ssq1;
-      s0 += __shfl_xor(s0, 16, 64);
-      s0 += __shfl_xor(s0, 32, 64);
-      s1 += __shfl_xor(s1, 16, 64);
-      s1 += __shfl_xor(s1, 32, 64);
-      if (lane < 16) {
-        psred[wm * 128 + wn * 32 + lane] = s0;
-        psred[wm * 128 + wn * 32 + 16 + lane] = s1;
-      }
+      colnorm_reduce(psred, ssq0, ssq1, wn, wm, lane);
       __syncthreads();
       if (tid < 128) {
         bool out = true;   // (columns past M have nothing to lose)
         if (blk * DBN + tid < a.M) {
-          const double s = (psred[tid] + psred[128 + tid]) + (psred[256 + tid] + psred[384 + tid]);
+          const double s = colnorm_read(psred + tid);
           const double ub = acq_tail(ACQ_EI, a.acq_param, pmean[tid], fmax(variance - s, VAR_FLOOR), a.m.noise);
           const double best = __longlong_as_double(
-              (long long)__hip_atomic_load(a.prune, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+              (long long)__hip_atomic_load(a.prune + PRUNE_W_BEST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
           out = best > PRUNE_MIN_BEST && ub * PRUNE_MARGIN < best;   // (a NaN bound compares false: never given up)
         }
         const int all_out = __all(out);
@@ -400,7 +398,7 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
     // PRUNE, split regime: a complete row block of C goes to the dump area as it stands, [survivor][row block][32][1024]
     // (thread-linear: coalesced); prune_fold_kernel folds it in fold_block's order.  Accumulators cleared.
     auto dump_block = [&](int ibd) {
-      double* dp = (double*)(a.prune + prune_dump_word(nblk)) + ((size_t)srv * nb + ibd) * PRUNE_DUMP_BLOCK + tid;
+      double* dp = pv().dump(srv, ibd, nb) + tid;
 #pragma unroll
       for (int fm = 0; fm < 4; ++fm)
 #pragma unroll
@@ -537,8 +535,8 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
         if (tid == 0) {
           a.blk_val[blk] = -INFINITY;   // as a block without a valid candidate
           a.blk_idx[blk] = INT64_MAX;
-          atomicAdd(a.prune + 1, 1ull);
-          atomicAdd(a.prune + 2, (unsigned long long)(nb - ib));
+          atomicAdd(a.prune + PRUNE_W_GIVEN_UP, 1ull);
+          atomicAdd(a.prune + PRUNE_W_SKIPPED, (unsigned long long)(nb - ib));
         }
         draw_next();  // LDS is rewritten by the next block
         continue;
@@ -546,64 +544,23 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
     }
     // ---- reductions (LDS is free after the last barrier; no DMA is outstanding) --------------------------
     if constexpr (!PRUNE) mred[krg * 128 + kcol] = macc;
-    {
-      double s0 = ssq0, s1 = ssq1;
-      s0 += __shfl_xor(s0, 16, 64);
-      s0 += __shfl_xor(s0, 32, 64);
-      s1 += __shfl_xor(s1, 16, 64);
-      s1 += __shfl_xor(s1, 32, 64);
-      if (lane < 16) {
-        sred[wm * 128 + wn * 32 + lane] = s0;
-        sred[wm * 128 + wn * 32 + 16 + lane] = s1;
-      }
-    }
+    colnorm_reduce(sred, ssq0, ssq1, wn, wm, lane);
     __syncthreads();
     double val = -INFINITY;
     int64_t gidx = INT64_MAX;
     if (tid < 128) {
       const int64_t cj = blk * DBN + tid;
       if (cj < a.M) {
-        double m = 0.0;
-        if constexpr (!PRUNE) {
-#pragma unroll
-          for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
-        }
-        const double mean = PRUNE ? pmean[tid] : m + a.m.mean_const;
-        const double s = (sred[tid] + sred[128 + tid]) + (sred[256 + tid] + sred[384 + tid]);
-        const double var = fmax(variance - s, VAR_FLOOR);
-        if (a.mean_out) a.mean_out[cj] = mean;
-        if (a.var_out) a.var_out[cj] = var;
-        if (a.acq_kind >= 0) {
-          const double v = acq_tail(a.acq_kind, a.acq_param, mean, var, a.m.noise);
-          if (a.acq_out) a.acq_out[cj] = v;
-          if (!(v != v)) {
-            val = v;
-            gidx = a.index_base + cj;
-          }
-        }
+        double mean;
+        if constexpr (PRUNE) mean = pmean[tid];
+        else mean = mean_reduce(a, mred, tid);
+        sweep_tail(a, cj, mean, fmax(variance - colnorm_read(sred + tid), VAR_FLOOR), val, gidx);
       }
     }
     if (a.blk_val) {
-      if (tid < 128) {
-        wave_argmax(val, gidx);
-        if (lane == 0) {
-          bvs[w] = val;
-          bis[w] = gidx;
-        }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        double v0 = bvs[0];
-        int64_t i0 = bis[0];
-        if (better(bvs[1], bis[1], v0, i0)) {
-          v0 = bvs[1];
-          i0 = bis[1];
-        }
-        a.blk_val[blk] = v0;
-        a.blk_idx[blk] = i0;
-        if constexpr (PRUNE) {   // EI >= 0: the bit patterns order like the values (a -0.0 or a rounded-negative value stays out)
-          if (v0 > 0.0) atomicMax(a.prune, (unsigned long long)__double_as_longlong(v0));
-        }
+      const double v0 = block_winner(a, blk, val, gidx, bvs, bis, tid, w);
+      if constexpr (PRUNE) {   // EI >= 0: the bit patterns order like the values (a -0.0 or a rounded-negative value stays out)
+        if (tid == 0 && v0 > 0.0) atomicMax(a.prune + PRUNE_W_BEST, (unsigned long long)__double_as_longlong(v0));
       }
     }
     if constexpr (PRUNE) draw_next();
@@ -627,38 +584,21 @@ __global__ __launch_bounds__(1024, WAVES) void prune_mean_kernel(const SweepArgs
   const int kcol = tid & 127;
   const int krg = __builtin_amdgcn_readfirstlane(tid >> 7);
   const int nb = (int)(a.m.Npad / DBM);
-  const int d = a.m.d;
   const double variance = a.m.variance;
   const int64_t nblk = (a.M + DBN - 1) / DBN;
-  double* const ubs = (double*)(a.prune + PRUNE_HDR_WORDS);
-  double* const means = (double*)(a.prune + PRUNE_HDR_WORDS + 2 * nblk);
+  const PruneView pv{a.prune, nblk};
   const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN);
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    for (int e = tid; e < DBN * DP; e += 1024) {  // scale the block's candidates once (c-major)
-      const int j = e / DP, c = e % DP;
-      const int64_t cand = blk * DBN + j;
-      const int64_t src = cand < a.M ? cand : 0;
-      xqs[c * DBN + j] = (c < d) ? a.Xq[src * d + c] / as_const(a.m.ls)[c] : 0.0;
-    }
+    for (int e = tid; e < DBN * DP; e += 1024) scale_entry(xqs, a.Xq, a.M, a.m.d, a.m.ls, blk, e / DP, e % DP);
     __syncthreads();
     double macc = 0.0;
     prune_generate<KIND, DP, GEN_MEAN>(a, xqs, kcol, krg, nb * DKSTEPS, nullptr, variance, macc);
     mred[krg * 128 + kcol] = macc;
     __syncthreads();
     if (tid < 128) {
-      double m = 0.0;
-#pragma unroll
-      for (int g = 0; g < 8; ++g) m += mred[g * 128 + tid];
-      const double pm = m + a.m.mean_const;
-      means[blk * DBN + tid] = pm;
+      const double pm = pv.means()[blk * DBN + tid] = mean_reduce(a, mred, tid);
       const bool valid = blk * DBN + tid < a.M;
-      if (screen) {   // the seed: the block's largest eta - mean over valid columns (a NaN mean posts nothing)
-        double seed = valid ? a.acq_param - pm : 0.0;
-        if (!(seed > 0.0)) seed = 0.0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) seed = fmax(seed, __shfl_xor(seed, o, 64));
-        if (lane == 0 && seed > 0.0) atomicMax(a.prune, (unsigned long long)__double_as_longlong(seed));
-      }
+      if (screen) post_seed(a, valid, pm, lane);
       // the checkpoint's bound with an empty partial norm; columns past M have nothing to lose
       double ub = -INFINITY;
       if (valid) {
@@ -670,28 +610,8 @@ __global__ __launch_bounds__(1024, WAVES) void prune_mean_kernel(const SweepArgs
       if (lane == 0) ubw[w] = ub;
     }
     __syncthreads();   // xqs and mred are rewritten by the next block
-    if (tid == 0) ubs[blk] = fmax(ubw[0], ubw[1]);
+    if (tid == 0) pv.bounds()[blk] = fmax(ubw[0], ubw[1]);
   }
-}
-
-// ranges of roughly equal triangular work over nb row blocks (plan_split of the host side); single row blocks when g == nb
-__device__ bool prune_plan(unsigned long long* ibw, int nb, int g) {
-  if (g == nb) {
-    for (int k = 0; k <= g; ++k) ibw[k] = (unsigned long long)k;
-    return true;
-  }
-  const int total = nb * (nb + 1) / 2;
-  ibw[0] = 0;
-  int ib = 0;
-  for (int k = 1; k < g; ++k) {
-    while (ib < nb && ib * (ib + 1) / 2 < (int)((int64_t)total * k / g)) ++ib;
-    const int prev = (int)ibw[k - 1] + 1;
-    ibw[k] = (unsigned long long)(ib > prev ? ib : prev);
-  }
-  ibw[g] = (unsigned long long)nb;
-  bool ok = true;
-  for (int k = 0; k < g; ++k) ok = ok && ibw[k] < ibw[k + 1];
-  return ok;
 }
 
 // Between phases 1 and 2, one workgroup: the give-up rule per block on the stored bound against the best word, which now
@@ -703,9 +623,10 @@ __global__ __launch_bounds__(1024) void prune_list_kernel(const SweepArgs a, con
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int nb = (int)(a.m.Npad / DBM);
   const int64_t nblk = (a.M + DBN - 1) / DBN;
-  const double* ubs = (const double*)(a.prune + PRUNE_HDR_WORDS);
-  int64_t* list = (int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk);
-  const double best = __longlong_as_double((long long)a.prune[0]);
+  const PruneView pv{a.prune, nblk};
+  const double* ubs = pv.bounds();
+  int64_t* list = pv.list();
+  const double best = __longlong_as_double((long long)a.prune[PRUNE_W_BEST]);
   const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN) && best > PRUNE_MIN_BEST;
   int64_t base = 0;
   for (int64_t c0 = 0; c0 < nblk; c0 += 1024) {
@@ -732,9 +653,9 @@ __global__ __launch_bounds__(1024) void prune_list_kernel(const SweepArgs a, con
   }
   if (tid == 0) {
     const int64_t S = base, out = nblk - S;
-    a.prune[1] += (unsigned long long)out;
-    a.prune[2] += (unsigned long long)(out * (nb - 1));   // row blocks behind the first that are not computed
-    a.prune[3] += (unsigned long long)out;                // ... and the first is not either
+    a.prune[PRUNE_W_GIVEN_UP] += (unsigned long long)out;
+    a.prune[PRUNE_W_SKIPPED] += (unsigned long long)(out * (nb - 1));   // row blocks behind the first that are not computed
+    a.prune[PRUNE_W_SCREENED] += (unsigned long long)out;               // ... and the first is not either
     a.prune[PRUNE_W_SURVIVORS] = (unsigned long long)S;
     int groups = 0;
     if (S >= 1 && S <= (int64_t)pl.max_survivors && S <= (int64_t)wg) {   // split regime
@@ -742,7 +663,7 @@ __global__ __launch_bounds__(1024) void prune_list_kernel(const SweepArgs a, con
       if (groups > nb) groups = nb;
       if (groups > PRUNE_MAX_GROUPS) groups = PRUNE_MAX_GROUPS;
       if (pl.max_groups > 0 && groups > pl.max_groups) groups = pl.max_groups;
-      while (!prune_plan(a.prune + PRUNE_W_IB, nb, groups)) --groups;   // (one range always works)
+      while (!plan_row_split(a.prune + PRUNE_W_IB, nb, groups, true)) --groups;   // (one range always works)
     }
     a.prune[PRUNE_W_GROUPS] = (unsigned long long)groups;
     a.prune[PRUNE_W_ITEMS] = (unsigned long long)(S * groups);
@@ -762,9 +683,9 @@ __global__ __launch_bounds__(1024) void prune_fold_kernel(const SweepArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 2, wn = w & 3;
   const int nb = (int)(a.m.Npad / DBM);
-  const int64_t blk = ((const int64_t*)(a.prune + PRUNE_HDR_WORDS + nblk))[blockIdx.x];
-  const double* means = (const double*)(a.prune + PRUNE_HDR_WORDS + 2 * nblk);
-  const double* dp = (const double*)(a.prune + prune_dump_word(nblk)) + (size_t)blockIdx.x * nb * PRUNE_DUMP_BLOCK + tid;
+  const PruneView pv{a.prune, nblk};
+  const int64_t blk = pv.list()[blockIdx.x];
+  const double* dp = pv.dump(blockIdx.x, 0, nb) + tid;
   double ssq0 = 0.0, ssq1 = 0.0;
   for (int ib = 0; ib < nb; ++ib, dp += PRUNE_DUMP_BLOCK) {
 #pragma unroll
@@ -776,49 +697,14 @@ __global__ __launch_bounds__(1024) void prune_fold_kernel(const SweepArgs a) {
         ssq1 = fma(c1, c1, ssq1);
       }
   }
-  {
-    double s0 = ssq0, s1 = ssq1;
-    s0 += __shfl_xor(s0, 16, 64);
-    s0 += __shfl_xor(s0, 32, 64);
-    s1 += __shfl_xor(s1, 16, 64);
-    s1 += __shfl_xor(s1, 32, 64);
-    if (lane < 16) {
-      sred[wm * 128 + wn * 32 + lane] = s0;
-      sred[wm * 128 + wn * 32 + 16 + lane] = s1;
-    }
-  }
+  colnorm_reduce(sred, ssq0, ssq1, wn, wm, lane);
   __syncthreads();
   double val = -INFINITY;
   int64_t gidx = INT64_MAX;
-  if (tid < 128) {
-    const int64_t cj = blk * DBN + tid;
-    if (cj < a.M) {
-      const double mean = means[cj];
-      const double s = (sred[tid] + sred[128 + tid]) + (sred[256 + tid] + sred[384 + tid]);
-      const double var = fmax(a.m.variance - s, VAR_FLOOR);
-      const double v = acq_tail(a.acq_kind, a.acq_param, mean, var, a.m.noise);
-      if (!(v != v)) {
-        val = v;
-        gidx = a.index_base + cj;
-      }
-    }
-    wave_argmax(val, gidx);
-    if (lane == 0) {
-      bvs[w] = val;
-      bis[w] = gidx;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double v0 = bvs[0];
-    int64_t i0 = bis[0];
-    if (better(bvs[1], bis[1], v0, i0)) {
-      v0 = bvs[1];
-      i0 = bis[1];
-    }
-    a.blk_val[blk] = v0;
-    a.blk_idx[blk] = i0;
-  }
+  const int64_t cj = blk * DBN + tid;
+  if (tid < 128 && cj < a.M)
+    sweep_tail(a, cj, pv.means()[cj], fmax(a.m.variance - colnorm_read(sred + tid), VAR_FLOOR), val, gidx);
+  block_winner(a, blk, val, gidx, bvs, bis, tid, w);
 }
 
 template <int KIND, int DP>
