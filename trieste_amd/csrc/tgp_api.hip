@@ -109,6 +109,40 @@ int sync(tgp_handle h) {
   return TGP_OK;
 }
 
+// how a synchronising call ends: the stream drained, no launch of the call left an error behind
+int finish(tgp_handle h) {
+  if (int rc = sync(h)) return rc;
+  HIPCHK(h, hipGetLastError());
+  return TGP_OK;
+}
+
+constexpr const char* QEI_NOT_PD = "qEI: cov + jitter*I not positive definite for group %d";
+constexpr const char* BEI_NOT_PD = "batch EI: a covariance of group %d is not positive definite (after the 1e-6 jitters)";
+// d_info after the stream has drained: the 1-based group a device factorisation broke down at -> TGP_ERR_NOT_PD with `fmt`
+// (one %d: the 0-based group), else the call's launch check
+int info_finish(tgp_handle h, const char* fmt) {
+  int info = 0;
+  HIPCHK(h, hipMemcpy(&info, h->d_info.p, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipGetLastError());
+  if (info != 0) return fail(h, TGP_ERR_NOT_PD, fmt, info - 1);
+  return TGP_OK;
+}
+
+// One scratch buffer as a list of arrays: the caller names each pointer and its element count, the ONE reserve and the
+// pointers both come from that list (tgp_host.hpp scratch_offsets).  An array of count 0 gets a pointer nobody may use.
+struct Slot {
+  double** ptr;
+  size_t count;
+};
+template <int K>
+int carve(tgp_handle h, DevBuf& buf, const Slot (&slots)[K]) {
+  size_t counts[K], offsets[K];
+  for (int i = 0; i < K; ++i) counts[i] = slots[i].count;
+  HIPCHK(h, buf.reserve(scratch_offsets(counts, K, offsets) * sizeof(double)));
+  for (int i = 0; i < K; ++i) *slots[i].ptr = buf.as<double>() + offsets[i];
+  return TGP_OK;
+}
+
 int set_device(tgp_handle h) {
   HIPCHK(h, hipSetDevice(h->device));
   // hipGetLastError is per host thread and sticky: an error left behind by ANY earlier runtime call on
@@ -264,6 +298,52 @@ static bool auto_canary_tripped(tgp_handle h) {
   h->auto_pinned = false;
   (void)resolve_precision(h);
   return true;
+}
+// The winner of an arg-max: its device slots (value, index), their read-back, and what the caller asked for of it.
+struct Winner {
+  double* fv = nullptr;    // device slots in s_small
+  int64_t* fi = nullptr;
+  double hv = 0.0;         // host copies: valid after the synchronisation that follows enqueue_read
+  int64_t hi = 0;
+  int slots(tgp_handle h) {
+    HIPCHK(h, h->s_small.reserve(64));
+    fv = h->s_small.as<double>();
+    fi = (int64_t*)(fv + 1);
+    return TGP_OK;
+  }
+  int enqueue_read(tgp_handle h) {
+    HIPCHK(h, hipMemcpyAsync(&hv, fv, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&hi, fi, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    return TGP_OK;
+  }
+  // value, global index and (best_x) the winning row of the M candidates: Xq as the caller gave it, dXq on the device
+  int give(tgp_handle h, const double* Xq, const double* dXq, int64_t M, int64_t index_base, int where, double* best_val,
+           int64_t* best_idx, double* best_x) const {
+    if (best_val) *best_val = hv;
+    if (best_idx) *best_idx = hi;
+    if (best_x) {
+      const int64_t local = hi - index_base;
+      if (local < 0 || local >= M) return fail(h, TGP_ERR_HIP, "arg-max produced no valid index (all NaN?)");
+      if (where == TGP_DEVICE)
+        HIPCHK(h, hipMemcpy(best_x, dXq + local * h->d, h->d * sizeof(double), hipMemcpyDeviceToHost));
+      else
+        memcpy(best_x, Xq + local * h->d, h->d * sizeof(double));
+    }
+    return TGP_OK;
+  }
+};
+
+// `enqueue` (sweeps and the copies of their results), the synchronisation, and both again -- twice at most -- while a
+// canary fired (TGP_PREC_AUTO: a sample broke its bound -> next rung, again)
+template <class Enqueue>
+int finish_with_canary_retry(tgp_handle h, Enqueue enqueue) {
+  for (int attempt = 0;; ++attempt) {
+    if (int rc = enqueue()) return rc;
+    if (int rc = finish(h)) return rc;
+    if (attempt < 2 && auto_canary_tripped(h)) continue;
+    break;
+  }
+  return TGP_OK;
 }
 
 // number of per-block winner slots a fused arg-max over `a` fills (one per candidate block of the kernel in use)
@@ -808,6 +888,82 @@ int gemm_tall(tgp_handle h, bool tb, int m, int n, int k, double alpha, const do
     launch_gemm(h->stream, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, false, tri);
   }
   return TGP_OK;
+}
+
+// ---- the stages of the "small-product" posterior at P (padded: Ppad) resident points, each written once ------------------------
+// B [ld][Ppad] = K*^T = k(X, Xq) of the model `m` and, unless C1 is null, C1 = W B (W = L^-1 of that model, lower
+// triangular incl. explicit zeros, leading dimension ld): the model's own, the repulsion twin's, either side of a cross-covariance
+int kstar_products(tgp_handle h, const ModelDev& m, const double* W, int64_t ld, const double* dXq, int64_t P, int64_t Ppad,
+                   double* B, double* C1) {
+  launch_kstar_t(h->stream, m, dXq, P, Ppad, B);
+  if (!C1) return TGP_OK;
+  return gemm_tall(h, false, (int)ld, (int)Ppad, (int)ld, 1.0, W, ld, B, Ppad, 0.0, C1, Ppad, 3);
+}
+// Z [ld][Ppad] = W^T D (Wt, upper triangular; D = C1 gives K^-1 k*)
+int wt_product(tgp_handle h, const double* Wt, int64_t ld, const double* D, int64_t Ppad, double* Z) {
+  return gemm_tall(h, false, (int)ld, (int)Ppad, (int)ld, 1.0, Wt, ld, D, Ppad, 0.0, Z, Ppad, 5);
+}
+// the Gram product S [P1p][P2p] = C1^T C2 of two W K* arrays [Npad][P1p], [Npad][P2p]; C1t [P1p][Npad] takes the transpose
+int gram_product(tgp_handle h, int64_t Npad, const double* C1, int64_t P1p, double* C1t, const double* C2, int64_t P2p, double* S) {
+  launch_transpose(h->stream, C1, Npad, P1p, P1p, C1t, Npad);
+  return gemm_tall(h, false, (int)P1p, (int)P2p, (int)Npad, 1.0, C1t, Npad, C2, P2p, 0.0, S, P2p, 0);
+}
+
+// The arrays of the joint posterior of P = G q points and of its vector-Jacobian product, carved from s_grad.  FORWARD needs
+// B, C1, T (C1^T), S and the small-predict tail's partial sums; BACKWARD B, C1, T (the mixed D), Z and the gradient tail's;
+// a value-and-gradient call needs both on the SAME K*^T and W K*, and the moments and their adjoints in between.
+struct JointScratch {
+  double *B, *C1, *T, *Z, *S, *part;
+  double *mean, *cov, *gmean, *gcov;   // [P], [P][q] each: only where both halves run
+};
+constexpr int JOINT_FORWARD = 1, JOINT_BACKWARD = 2;
+int joint_scratch(tgp_handle h, int64_t P, int64_t Ppad, int q, int halves, JointScratch& w) {
+  const bool fwd = halves & JOINT_FORWARD, bwd = halves & JOINT_BACKWARD;
+  const size_t np = (size_t)h->Npad * Ppad, moments = fwd && bwd ? (size_t)P : 0;
+  const size_t part = std::max(fwd ? predict_small_scratch_doubles(Ppad) : 0, bwd ? grad_tail_scratch_doubles(Ppad, h->dp) : 0);
+  return carve(h, h->s_grad, {{&w.B, np}, {&w.C1, np}, {&w.T, np}, {&w.Z, bwd ? np : 0}, {&w.S, fwd ? (size_t)Ppad * Ppad : 0},
+                              {&w.part, part}, {&w.mean, moments}, {&w.cov, moments * q}, {&w.gmean, moments},
+                              {&w.gcov, moments * q}});
+}
+// forward half: mean [P], cov [P][q] (device): K*^T, W K*, ONE Gram product, the small-predict tail, the pick kernel
+int joint_forward(tgp_handle h, const JointScratch& w, const double* dXq, int64_t P, int64_t Ppad, int q, double* dmean, double* dcov) {
+  const ModelDev m = model_dev(h);
+  if (int rc = kstar_products(h, m, h->d_W.as<double>(), h->Npad, dXq, P, Ppad, w.B, w.C1)) return rc;
+  if (int rc = gram_product(h, h->Npad, w.C1, Ppad, w.T, w.C1, Ppad, w.S)) return rc;
+  launch_predict_small_tail(h->stream, m, P, Ppad, w.B, w.C1, w.part, dmean, nullptr);
+  launch_joint_pick(h->stream, m, dXq, P, Ppad, q, w.S, dcov);
+  return TGP_OK;
+}
+// backward half, on the forward half's (or kstar_products') B and C1: the adjoints dgm [P], dgc [P][q] of mean and covariance
+// -> dgrad [P][d]: the mix kernel, the Wt product, the vjp tail
+int joint_backward(tgp_handle h, const JointScratch& w, const double* dXq, int64_t P, int64_t Ppad, int q, const double* dgm,
+                   const double* dgc, double* dgrad) {
+  launch_joint_mix(h->stream, w.C1, dgc, P, Ppad, h->Npad, q, w.T);
+  if (int rc = wt_product(h, h->d_A.as<double>(), h->Npad, w.T, Ppad, w.Z)) return rc;
+  launch_joint_vjp_tail(h->stream, model_dev(h), dXq, P, Ppad, q, w.B, w.C1, w.Z, w.part, dgm, dgc, dgrad);
+  return TGP_OK;
+}
+// Value [G] and gradient [P][d] of a batch acquisition function over G groups of q resident points in ONE call, everything on
+// the device: the forward half -> `tail(mean, cov, dval, gmean, gcov)` (the caller's one-wave-per-group kernel: value and the
+// adjoints of mean and covariance; it reports a breakdown through d_info) -> the backward half on the SAME K*^T and W K*.
+// One host synchronisation; `not_pd`: info_finish's message.
+template <class Tail>
+int joint_value_grad(tgp_handle h, const double* dXq, int64_t G, int q, int64_t P, int64_t Ppad, double* val, double* grad,
+                     int where, const char* not_pd, Tail tail) {
+  double *dval, *dgrad;
+  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)P * h->d, where, &dgrad)) return rc;
+  JointScratch w;
+  if (int rc = joint_scratch(h, P, Ppad, q, JOINT_FORWARD | JOINT_BACKWARD, w)) return rc;
+  HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  if (int rc = joint_forward(h, w, dXq, P, Ppad, q, w.mean, w.cov)) return rc;
+  tail(w.mean, w.cov, dval, w.gmean, w.gcov);
+  if (int rc = joint_backward(h, w, dXq, P, Ppad, q, w.gmean, w.gcov, dgrad)) return rc;
+  if (int rc = stage_out_finish(h, dval, val, (size_t)G, where)) return rc;
+  if (int rc = stage_out_finish(h, dgrad, grad, (size_t)P * h->d, where)) return rc;
+  if (int rc = sync(h)) return rc;
+  return info_finish(h, not_pd);
 }
 
 constexpr int ACQ_KIND_MAX = TGP_ACQ_GIBBON;  // public kinds: EI, PI, -LCB, AEI, MES, GIBBON
@@ -1752,9 +1908,7 @@ int tgp_penalization_values(tgp_handle h, const double* Xq, int64_t M, double* o
   launch_penalize(h->stream, dout, dXq, M, h->d, h->pen_kind, h->pen_P, pend, pend + (size_t)h->pen_P * h->d,
                   pend + (size_t)h->pen_P * (h->d + 1), true);
   if (int rc = stage_out_finish(h, dout, out, M, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 int tgp_nlml(tgp_handle h, double* value, double* grad) {
@@ -1780,8 +1934,7 @@ int tgp_nlml(tgp_handle h, double* value, double* grad) {
   }
   std::vector<double> host((size_t)np);
   HIPCHK(h, hipMemcpyAsync(host.data(), out, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
+  if (int rc = finish(h)) return rc;
   *value = host[0];
   if (grad)
     for (int c = 0; c < h->d + 3; ++c) grad[c] = host[1 + c];
@@ -1817,15 +1970,11 @@ int tgp_get_factor(tgp_handle h, double* L, double* Winv, double* alpha, int whe
 static const int64_t SMALL_PREDICT_M = getenv("TGP_SMALL_PREDICT_M") ? atoll(getenv("TGP_SMALL_PREDICT_M")) : 2048;   // (env: development aid)
 static int predict_small(tgp_handle h, const double* dXq, int64_t M, double* dmean, double* dvar) {
   const int64_t Ppad = ((M + 63) / 64) * 64, Npad = h->Npad;
-  HIPCHK(h, h->s_grad.reserve(((size_t)2 * Npad * Ppad + predict_small_scratch_doubles(Ppad)) * sizeof(double)));
-  double* B = h->s_grad.as<double>();
-  double* C1 = B + (size_t)Npad * Ppad;
-  double* part = C1 + (size_t)Npad * Ppad;
+  double *B, *C1, *part;
+  if (int rc = carve(h, h->s_grad, {{&B, (size_t)Npad * Ppad}, {&C1, (size_t)Npad * Ppad}, {&part, predict_small_scratch_doubles(Ppad)}}))
+    return rc;
   const ModelDev m = model_dev(h);
-  launch_kstar_t(h->stream, m, dXq, M, Ppad, B);
-  if (dvar)
-    if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B, Ppad, 0.0, C1, Ppad, 3))
-      return rc;
+  if (int rc = kstar_products(h, m, h->d_W.as<double>(), Npad, dXq, M, Ppad, B, dvar ? C1 : nullptr)) return rc;
   launch_predict_small_tail(h->stream, m, M, Ppad, B, C1, part, dmean, dvar);
   h->last_launches = 0;
   h->last_ms = -1.0;
@@ -1860,22 +2009,15 @@ static int sweep_common(tgp_handle h, const double* Xq, int64_t M, double* mean,
     if (int rc = predict_small(h, dXq, M, a.mean_out, a.var_out)) return rc;
     if (int rc = stage_out_finish(h, a.mean_out, mean, M, where)) return rc;
     if (int rc = stage_out_finish(h, a.var_out, var, M, where)) return rc;
-    if (int rc = sync(h)) return rc;
-    HIPCHK(h, hipGetLastError());
-    return TGP_OK;
+    return finish(h);
   }
-  for (int attempt = 0;; ++attempt) {
+  return finish_with_canary_retry(h, [&]() -> int {
     HIPCHK(h, launch_sweep_timed(h, a, false));
     if (acq_kind >= 0) apply_penalization(h, a.acq_out, dXq, M);
     if (int rc = stage_out_finish(h, a.mean_out, mean, M, where)) return rc;
     if (int rc = stage_out_finish(h, a.var_out, var, M, where)) return rc;
-    if (int rc = stage_out_finish(h, a.acq_out, acq, M, where)) return rc;
-    if (int rc = sync(h)) return rc;
-    HIPCHK(h, hipGetLastError());
-    if (attempt < 2 && auto_canary_tripped(h)) continue;  // TGP_PREC_AUTO: a sample broke its bound -> next rung, again
-    break;
-  }
-  return TGP_OK;
+    return stage_out_finish(h, a.acq_out, acq, M, where);
+  });
 }
 
 int tgp_predict(tgp_handle h, const double* Xq, int64_t M, double* mean, double* var, int where) {
@@ -1894,9 +2036,7 @@ int tgp_predict_mean(tgp_handle h, const double* Xq, int64_t M, double* mean, in
   if (int rc = stage_out_prepare(h, h->s_out1, mean, M, where, &dmean)) return rc;
   launch_predict_mean(h->stream, model_dev(h), dXq, M, dmean);
   if (int rc = stage_out_finish(h, dmean, mean, M, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 int tgp_eta(tgp_handle h, double* eta) {
@@ -1908,9 +2048,7 @@ int tgp_eta(tgp_handle h, double* eta) {
   launch_predict_mean(h->stream, model_dev(h), h->d_X.as<double>(), h->N, h->s_out1.as<double>());
   launch_min_value(h->stream, h->s_out1.as<double>(), h->N, h->s_small.as<double>());
   HIPCHK(h, hipMemcpyAsync(eta, h->s_small.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 int tgp_acq_values(tgp_handle h, int acq_kind, double param, const double* Xq, int64_t M, double* out,
@@ -1927,15 +2065,10 @@ int tgp_acq_values(tgp_handle h, int acq_kind, double param, const double* Xq, i
     double* dout;
     if (int rc = stage_in(h, h->s_in, Xq, (size_t)M * h->d, where, &dXq)) return rc;
     if (int rc = stage_out_prepare(h, h->s_out3, out, M, where, &dout)) return rc;
-    for (int attempt = 0;; ++attempt) {
+    return finish_with_canary_retry(h, [&]() -> int {
       if (int rc = acq_values_device(h, acq_kind, param, dXq, M, dout)) return rc;
-      if (int rc = stage_out_finish(h, dout, out, M, where)) return rc;
-      if (int rc = sync(h)) return rc;
-      HIPCHK(h, hipGetLastError());
-      if (attempt < 2 && auto_canary_tripped(h)) continue;
-      break;
-    }
-    return TGP_OK;
+      return stage_out_finish(h, dout, out, M, where);
+    });
   }
   return sweep_common(h, Xq, M, nullptr, nullptr, out, acq_kind, param, where);
 }
@@ -1954,39 +2087,26 @@ int tgp_acq_value_grad(tgp_handle h, int acq_kind, double param, const double* X
   if (int rc = stage_in(h, h->s_in, Xq, (size_t)P * h->d, where, &dXq)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, val, P, where, &dval)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)P * h->d, where, &dgrad)) return rc;
-  const int64_t Nscratch = (acq_kind == TGP_ACQ_GIBBON && h->rep_twin) ? std::max(Npad, h->rep_twin->Npad) : Npad;
-  HIPCHK(h, h->s_grad.reserve(((size_t)3 * Nscratch * Ppad + grad_tail_scratch_doubles(Ppad, h->dp)) * sizeof(double)));
-  double* B = h->s_grad.as<double>();
-  double* C1 = B + (size_t)Npad * Ppad;
-  double* Z = C1 + (size_t)Npad * Ppad;
-  double* const gpart = B + (size_t)3 * Nscratch * Ppad;   // the gradient tail's partial sums
-  const ModelDev m = model_dev(h);
-  launch_kstar_t(h->stream, m, dXq, P, Ppad, B);
-  // C1 = W B (W = L^-1, lower triangular incl. explicit zeros), Z = W^T C1 = K^-1 k*
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B, Ppad, 0.0, C1,
-                         Ppad, 3)) return rc;
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_A.as<double>(), Npad, C1, Ppad, 0.0, Z,
-                         Ppad, 5)) return rc;
   if (acq_kind >= TGP_ACQ_MES && h->ent_S == 0)
     return fail(h, TGP_ERR_STATE, "entropy-search acquisition needs min-value samples: call tgp_set_min_value_samples");
   tgp_handle twin = acq_kind == TGP_ACQ_GIBBON ? h->rep_twin : nullptr;
-  launch_grad_tail(h->stream, m, dXq, P, Ppad, B, C1, Z, gpart, acq_kind, param, dval, dgrad, h->d_ent.as<double>(), h->ent_S,
-                   twin ? h->rep_weight : 0.0, 0.0);
-  if (twin) {  // + w/2 log(var_twin + noise): the same pipeline on the conditioned model, accumulated
-    if (!twin->have_data) return fail(h, TGP_ERR_STATE, "the repulsion twin has no data");
-    const int64_t Nt = twin->Npad;
-    double* Bt = h->s_grad.as<double>();
-    double* C1t = Bt + (size_t)Nt * Ppad;
-    double* Zt = C1t + (size_t)Nt * Ppad;
-    const ModelDev mt = model_dev(twin);
-    launch_kstar_t(h->stream, mt, dXq, P, Ppad, Bt);
-    if (int rc = gemm_tall(h, false, (int)Nt, (int)Ppad, (int)Nt, 1.0, twin->d_W.as<double>(), Nt, Bt, Ppad, 0.0, C1t,
-                           Ppad, 3)) return rc;
-    if (int rc = gemm_tall(h, false, (int)Nt, (int)Ppad, (int)Nt, 1.0, twin->d_A.as<double>(), Nt, C1t, Ppad, 0.0, Zt,
-                           Ppad, 5)) return rc;
-    launch_grad_tail(h->stream, mt, dXq, P, Ppad, Bt, C1t, Zt, gpart, ACQ_LOGYVAR, 0.0, dval, dgrad, nullptr, 0, 0.0,
-                     0.5 * h->rep_weight);
-  }
+  if (twin && !twin->have_data) return fail(h, TGP_ERR_STATE, "the repulsion twin has no data");
+  // the twin's pass reuses the model's three arrays: they are sized by the larger of the two padded sizes
+  const size_t np = (size_t)(twin ? std::max(Npad, twin->Npad) : Npad) * Ppad;
+  double *B, *C1, *Z, *gpart;   // (gpart: the gradient tail's partial sums)
+  if (int rc = carve(h, h->s_grad, {{&B, np}, {&C1, np}, {&Z, np}, {&gpart, grad_tail_scratch_doubles(Ppad, h->dp)}})) return rc;
+  // B = K*^T, C1 = W B, Z = W^T C1 = K^-1 k* of the model `t`, then its gradient tail
+  auto pass = [&](tgp_handle t, int kind, double par, const double* samples, int S, double rep_w, double accum) -> int {
+    const ModelDev m = model_dev(t);
+    if (int rc = kstar_products(h, m, t->d_W.as<double>(), t->Npad, dXq, P, Ppad, B, C1)) return rc;
+    if (int rc = wt_product(h, t->d_A.as<double>(), t->Npad, C1, Ppad, Z)) return rc;
+    launch_grad_tail(h->stream, m, dXq, P, Ppad, B, C1, Z, gpart, kind, par, dval, dgrad, samples, S, rep_w, accum);
+    return TGP_OK;
+  };
+  if (int rc = pass(h, acq_kind, param, h->d_ent.as<double>(), h->ent_S, twin ? h->rep_weight : 0.0, 0.0)) return rc;
+  // + w/2 log(var_twin + noise): the same pipeline on the conditioned model, accumulated
+  if (twin)
+    if (int rc = pass(twin, ACQ_LOGYVAR, 0.0, nullptr, 0, 0.0, 0.5 * h->rep_weight)) return rc;
   if (h->pen_kind != 0 && h->pen_P > 0) {
     const double* pend = h->d_pen.as<double>();
     launch_penalize_grad(h->stream, dval, dgrad, dXq, P, h->d, h->pen_kind, h->pen_P, pend,
@@ -1994,9 +2114,7 @@ int tgp_acq_value_grad(tgp_handle h, int acq_kind, double param, const double* X
   }
   if (int rc = stage_out_finish(h, dval, val, P, where)) return rc;
   if (int rc = stage_out_finish(h, dgrad, grad, (size_t)P * h->d, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 // ---- the handful of q-batches of an L-BFGS-B iteration over a BATCH acquisition function (qEI; round 6) ------------------------
@@ -2022,23 +2140,9 @@ static int joint_small_common(tgp_handle h, const double* Xq, int64_t G, int q, 
 
 // mean [P], cov [P][q] (device) of P = G q resident points: K*^T, W K*, ONE Gram product, the small-predict tail, the pick kernel
 static int joint_small_device(tgp_handle h, const double* dXq, int64_t P, int64_t Ppad, int q, double* dmean, double* dcov) {
-  const int64_t Npad = h->Npad;
-  HIPCHK(h, h->s_grad.reserve(((size_t)3 * Npad * Ppad + (size_t)Ppad * Ppad + predict_small_scratch_doubles(Ppad)) *
-                              sizeof(double)));
-  double* B = h->s_grad.as<double>();
-  double* C1 = B + (size_t)Npad * Ppad;
-  double* C1t = C1 + (size_t)Npad * Ppad;
-  double* S = C1t + (size_t)Npad * Ppad;
-  double* part = S + (size_t)Ppad * Ppad;
-  const ModelDev m = model_dev(h);
-  launch_kstar_t(h->stream, m, dXq, P, Ppad, B);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B, Ppad, 0.0, C1, Ppad, 3))
-    return rc;
-  launch_transpose(h->stream, C1, Npad, Ppad, Ppad, C1t, Npad);
-  if (int rc = gemm_tall(h, false, (int)Ppad, (int)Ppad, (int)Npad, 1.0, C1t, Npad, C1, Ppad, 0.0, S, Ppad, 0)) return rc;
-  launch_predict_small_tail(h->stream, m, P, Ppad, B, C1, part, dmean, nullptr);
-  launch_joint_pick(h->stream, m, dXq, P, Ppad, q, S, dcov);
-  return TGP_OK;
+  JointScratch w;
+  if (int rc = joint_scratch(h, P, Ppad, q, JOINT_FORWARD, w)) return rc;
+  return joint_forward(h, w, dXq, P, Ppad, q, dmean, dcov);
 }
 
 int tgp_joint_forward(tgp_handle h, const double* Xq, int64_t G, int q, double* mean, double* cov, int where) {
@@ -2053,9 +2157,7 @@ int tgp_joint_forward(tgp_handle h, const double* Xq, int64_t G, int q, double* 
   if (int rc = joint_small_device(h, dXq, P, Ppad, q, dmean, dcov)) return rc;
   if (int rc = stage_out_finish(h, dmean, mean, (size_t)P, where)) return rc;
   if (int rc = stage_out_finish(h, dcov, cov, (size_t)P * q, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 int tgp_joint_vjp(tgp_handle h, const double* Xq, int64_t G, int q, const double* gmean, const double* gcov, double* grad,
@@ -2065,30 +2167,17 @@ int tgp_joint_vjp(tgp_handle h, const double* Xq, int64_t G, int q, const double
   const double* dXq;
   int64_t P, Ppad;
   if (int rc = joint_small_common(h, Xq, G, q, where, &dXq, &P, &Ppad)) return rc;
-  const int64_t Npad = h->Npad;
   const double *dgm, *dgc;
   double* dgrad;
   if (int rc = stage_in(h, h->s_in2, gmean, (size_t)P, where, &dgm)) return rc;
   if (int rc = stage_in(h, h->s_out2, gcov, (size_t)P * q, where, &dgc)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, grad, (size_t)P * h->d, where, &dgrad)) return rc;
-  HIPCHK(h, h->s_grad.reserve(((size_t)4 * Npad * Ppad + grad_tail_scratch_doubles(Ppad, h->dp)) * sizeof(double)));
-  double* B = h->s_grad.as<double>();
-  double* C1 = B + (size_t)Npad * Ppad;
-  double* D = C1 + (size_t)Npad * Ppad;
-  double* Z = D + (size_t)Npad * Ppad;
-  double* part = Z + (size_t)Npad * Ppad;
-  const ModelDev m = model_dev(h);
-  launch_kstar_t(h->stream, m, dXq, P, Ppad, B);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B, Ppad, 0.0, C1, Ppad, 3))
-    return rc;
-  launch_joint_mix(h->stream, C1, dgc, P, Ppad, Npad, q, D);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_A.as<double>(), Npad, D, Ppad, 0.0, Z, Ppad, 5))
-    return rc;
-  launch_joint_vjp_tail(h->stream, m, dXq, P, Ppad, q, B, C1, Z, part, dgm, dgc, dgrad);
+  JointScratch w;
+  if (int rc = joint_scratch(h, P, Ppad, q, JOINT_BACKWARD, w)) return rc;
+  if (int rc = kstar_products(h, model_dev(h), h->d_W.as<double>(), h->Npad, dXq, P, Ppad, w.B, w.C1)) return rc;
+  if (int rc = joint_backward(h, w, dXq, P, Ppad, q, dgm, dgc, dgrad)) return rc;
   if (int rc = stage_out_finish(h, dgrad, grad, (size_t)P * h->d, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 // qEI value and gradient of a handful of q-batches in ONE call, everything on the device: tgp_joint_forward's arrays -> the
@@ -2106,48 +2195,12 @@ int tgp_qei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, const d
   const double* dXq;
   int64_t P, Ppad;
   if (int rc = joint_small_common(h, Xq, G, q, where, &dXq, &P, &Ppad)) return rc;
-  const int64_t Npad = h->Npad;
   const double* deps;
-  double *dval, *dgrad;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)P * h->d, where, &dgrad)) return rc;
-  const size_t part_doubles = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, h->dp));
-  HIPCHK(h, h->s_grad.reserve(((size_t)4 * Npad * Ppad + (size_t)Ppad * Ppad + part_doubles + (size_t)2 * P * (1 + q)) * sizeof(double)));
-  double* B = h->s_grad.as<double>();
-  double* C1 = B + (size_t)Npad * Ppad;
-  double* T1 = C1 + (size_t)Npad * Ppad;   // C1^T, then D
-  double* Z = T1 + (size_t)Npad * Ppad;
-  double* Spp = Z + (size_t)Npad * Ppad;
-  double* part = Spp + (size_t)Ppad * Ppad;
-  double* dmean = part + part_doubles;
-  double* dcov = dmean + P;
-  double* dgm = dcov + (size_t)P * q;
-  double* dgc = dgm + P;
-  const ModelDev m = model_dev(h);
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
-  launch_kstar_t(h->stream, m, dXq, P, Ppad, B);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B, Ppad, 0.0, C1, Ppad, 3))
-    return rc;
-  launch_transpose(h->stream, C1, Npad, Ppad, Ppad, T1, Npad);
-  if (int rc = gemm_tall(h, false, (int)Ppad, (int)Ppad, (int)Npad, 1.0, T1, Npad, C1, Ppad, 0.0, Spp, Ppad, 0)) return rc;
-  launch_predict_small_tail(h->stream, m, P, Ppad, B, C1, part, dmean, nullptr);
-  launch_joint_pick(h->stream, m, dXq, P, Ppad, q, Spp, dcov);
-  launch_qei_grad_tail(h->stream, dmean, dcov, G, q, deps, S, eta, jitter, dval, dgm, dgc, h->d_info.as<int>());
-  launch_joint_mix(h->stream, C1, dgc, P, Ppad, Npad, q, T1);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_A.as<double>(), Npad, T1, Ppad, 0.0, Z, Ppad, 5))
-    return rc;
-  launch_joint_vjp_tail(h->stream, m, dXq, P, Ppad, q, B, C1, Z, part, dgm, dgc, dgrad);
-  if (int rc = stage_out_finish(h, dval, val, (size_t)G, where)) return rc;
-  if (int rc = stage_out_finish(h, dgrad, grad, (size_t)P * h->d, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  int info = 0;
-  HIPCHK(h, hipMemcpy(&info, h->d_info.p, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(h, hipGetLastError());
-  if (info != 0)
-    return fail(h, TGP_ERR_NOT_PD, "qEI: cov + jitter*I not positive definite for group %d", info - 1);
-  return TGP_OK;
+  return joint_value_grad(h, dXq, G, q, P, Ppad, val, grad, where, QEI_NOT_PD,
+                          [&](const double* dmean, const double* dcov, double* dval, double* dgm, double* dgc) {
+                            launch_qei_grad_tail(h->stream, dmean, dcov, G, q, deps, S, eta, jitter, dval, dgm, dgc, h->d_info.as<int>());
+                          });
 }
 
 int tgp_cov_between(tgp_handle h, const double* X1, int64_t P1, const double* X2, int64_t P2, double* out,
@@ -2163,27 +2216,17 @@ int tgp_cov_between(tgp_handle h, const double* X1, int64_t P1, const double* X2
   if (int rc = stage_in(h, h->s_in, X1, (size_t)P1 * h->d, where, &d1)) return rc;
   if (int rc = stage_in(h, h->s_in2, X2, (size_t)P2 * h->d, where, &d2)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, out, (size_t)P1 * P2, where, &dout)) return rc;
-  HIPCHK(h, h->s_grad.reserve(((size_t)Npad * (3 * P1p + 2 * P2p) + (size_t)P1p * P2p) * sizeof(double)));
-  double* B1 = h->s_grad.as<double>();
-  double* C1 = B1 + (size_t)Npad * P1p;
-  double* C1t = C1 + (size_t)Npad * P1p;
-  double* B2 = C1t + (size_t)Npad * P1p;
-  double* C2 = B2 + (size_t)Npad * P2p;
-  double* S = C2 + (size_t)Npad * P2p;
+  const size_t np1 = (size_t)Npad * P1p, np2 = (size_t)Npad * P2p;
+  double *B1, *C1, *C1t, *B2, *C2, *S;
+  if (int rc = carve(h, h->s_grad, {{&B1, np1}, {&C1, np1}, {&C1t, np1}, {&B2, np2}, {&C2, np2}, {&S, (size_t)P1p * P2p}})) return rc;
   const ModelDev m = model_dev(h);
-  hipStream_t s = h->stream;
   // A_i = L^-1 K(X, X_i) = W B_i;  S = A_1^T A_2  (the reference's two triangular solves + einsum)
-  launch_kstar_t(s, m, d1, P1, P1p, B1);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)P1p, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B1, P1p, 0.0, C1, P1p, 3)) return rc;
-  launch_kstar_t(s, m, d2, P2, P2p, B2);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)P2p, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B2, P2p, 0.0, C2, P2p, 3)) return rc;
-  launch_transpose(s, C1, Npad, P1p, P1p, C1t, Npad);
-  if (int rc = gemm_tall(h, false, (int)P1p, (int)P2p, (int)Npad, 1.0, C1t, Npad, C2, P2p, 0.0, S, P2p, 0)) return rc;
-  launch_cov_tail(s, m, d1, P1, d2, P2, S, P2p, dout);
+  if (int rc = kstar_products(h, m, h->d_W.as<double>(), Npad, d1, P1, P1p, B1, C1)) return rc;
+  if (int rc = kstar_products(h, m, h->d_W.as<double>(), Npad, d2, P2, P2p, B2, C2)) return rc;
+  if (int rc = gram_product(h, Npad, C1, P1p, C1t, C2, P2p, S)) return rc;
+  launch_cov_tail(h->stream, m, d1, P1, d2, P2, S, P2p, dout);
   if (int rc = stage_out_finish(h, dout, out, (size_t)P1 * P2, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 int tgp_sample_joint(tgp_handle h, const double* Xq, int64_t n, const double* eps, int S, double jitter,
@@ -2199,18 +2242,13 @@ int tgp_sample_joint(tgp_handle h, const double* Xq, int64_t n, const double* ep
   if (int rc = stage_in(h, h->s_in, Xq, (size_t)n * h->d, where, &dXq)) return rc;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)n * S, where, &deps)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, out, (size_t)S * n, where, &dout)) return rc;
-  const size_t need = (size_t)Npad * Pp * 3 + (size_t)Pp * Pp * 3 + (size_t)Pp * Sp * 2 + (size_t)Pp + 64;
-  HIPCHK(h, h->s_grad.reserve(need * sizeof(double)));
-  double* B1 = h->s_grad.as<double>();
-  double* C1 = B1 + (size_t)Npad * Pp;
-  double* C1t = C1 + (size_t)Npad * Pp;
-  double* A = C1t + (size_t)Npad * Pp;  // [Pp, Pp] covariance, then scratch of the factorisation
-  double* L = A + (size_t)Pp * Pp;
-  double* W = L + (size_t)Pp * Pp;
-  double* E = W + (size_t)Pp * Pp;      // [Pp, Sp] padded draws
-  double* R = E + (size_t)Pp * Sp;      // [Pp, Sp] L E
-  double* mean = R + (size_t)Pp * Sp;   // [Pp]
-  int* info = (int*)(mean + Pp);
+  // A: [Pp, Pp] covariance, then scratch of the factorisation; E: [Pp, Sp] padded draws; R: [Pp, Sp] L E; mean [Pp]
+  const size_t np = (size_t)Npad * Pp, pp = (size_t)Pp * Pp, ps = (size_t)Pp * Sp;
+  double *B1, *C1, *C1t, *A, *L, *W, *E, *R, *mean, *info_slot;
+  if (int rc = carve(h, h->s_grad, {{&B1, np}, {&C1, np}, {&C1t, np}, {&A, pp}, {&L, pp}, {&W, pp}, {&E, ps}, {&R, ps},
+                                    {&mean, (size_t)Pp}, {&info_slot, 64}}))
+    return rc;
+  int* info = (int*)info_slot;
   const ModelDev m = model_dev(h);
   hipStream_t s = h->stream;
   HIPCHK(h, hipMemsetAsync(info, 0, sizeof(int), s));
@@ -2230,8 +2268,7 @@ int tgp_sample_joint(tgp_handle h, const double* Xq, int64_t n, const double* ep
   int hinfo = 0;
   HIPCHK(h, hipMemcpyAsync(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost, s));
   if (int rc = stage_out_finish(h, dout, out, (size_t)S * n, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
+  if (int rc = finish(h)) return rc;
   if (hinfo != 0)
     return fail(h, TGP_ERR_NOT_PD, "Cholesky of the joint posterior covariance failed at point %d: increase the jitter",
                 hinfo - 1);
@@ -2301,31 +2338,14 @@ int tgp_acq_argmax(tgp_handle h, int acq_kind, double param, const double* Xq, i
   if (int rc = set_device(h)) return rc;
   const double* dXq;
   if (int rc = stage_in(h, h->s_in, Xq, (size_t)M * h->d, where, &dXq)) return rc;
-  HIPCHK(h, h->s_small.reserve(64));
-  double* fv = h->s_small.as<double>();
-  int64_t* fi = (int64_t*)(fv + 1);
-  double hv;
-  int64_t hi;
-  for (int attempt = 0;; ++attempt) {
-    if (int rc = enqueue_argmax(h, acq_kind, param, dXq, M, index_base, fv, fi)) return rc;
-    HIPCHK(h, hipMemcpyAsync(&hv, fv, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&hi, fi, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync(h)) return rc;
-    HIPCHK(h, hipGetLastError());
-    if (attempt < 2 && auto_canary_tripped(h)) continue;  // TGP_PREC_AUTO: a sample broke its bound -> next rung, again
-    break;
-  }
-  if (best_val) *best_val = hv;
-  if (best_idx) *best_idx = hi;
-  if (best_x) {
-    const int64_t local = hi - index_base;
-    if (local < 0 || local >= M) return fail(h, TGP_ERR_HIP, "arg-max produced no valid index (all NaN?)");
-    if (where == TGP_DEVICE)
-      HIPCHK(h, hipMemcpy(best_x, dXq + local * h->d, h->d * sizeof(double), hipMemcpyDeviceToHost));
-    else
-      memcpy(best_x, Xq + local * h->d, h->d * sizeof(double));
-  }
-  return TGP_OK;
+  Winner w;
+  if (int rc = w.slots(h)) return rc;
+  if (int rc = finish_with_canary_retry(h, [&]() -> int {
+        if (int rc = enqueue_argmax(h, acq_kind, param, dXq, M, index_base, w.fv, w.fi)) return rc;
+        return w.enqueue_read(h);
+      }))
+    return rc;
+  return w.give(h, Xq, dXq, M, index_base, where, best_val, best_idx, best_x);
 }
 
 int tgp_acq_argmax_async(tgp_handle h, int acq_kind, double param, const double* Xq_device, int64_t M,
@@ -2365,17 +2385,13 @@ int tgp_acq_topk(tgp_handle h, int acq_kind, double param, const double* Xq, int
   HIPCHK(h, h->s_small.reserve((size_t)k * 16 + 64));
   double* fv = h->s_small.as<double>();       // [k] winners' values
   int64_t* fi = (int64_t*)(fv + k);           // [k] winners' indices
-  for (int attempt = 0;; ++attempt) {
+  return finish_with_canary_retry(h, [&]() -> int {
     if (int rc = acq_values_device(h, acq_kind, param, dXq, M, dvals)) return rc;
     if (int rc = enqueue_topk_of_values(h, dvals, M, index_base, k, fv, fi)) return rc;
     HIPCHK(h, hipMemcpyAsync(vals, fv, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(idx, fi, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync(h)) return rc;
-    HIPCHK(h, hipGetLastError());
-    if (attempt < 2 && auto_canary_tripped(h)) continue;
-    break;
-  }
-  return TGP_OK;
+    return TGP_OK;
+  });
 }
 
 int tgp_sample_box(tgp_handle h, uint64_t seed, int64_t first, int64_t M, const double* lower,
@@ -2391,9 +2407,7 @@ int tgp_sample_box(tgp_handle h, uint64_t seed, int64_t first, int64_t M, const 
   HIPCHK(h, hipMemcpyAsync(dl, lower, h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(du, upper, h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   launch_sample_box(h->stream, seed, first, M, h->d, dl, du, out_device);
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 static int joint_common(tgp_handle h, const double* Xq, int64_t G, int q, int where, const double** dXq,
@@ -2446,10 +2460,56 @@ int tgp_predict_joint(tgp_handle h, const double* Xq, int64_t G, int q, double* 
   if (int rc = joint_common(h, Xq, G, q, where, &dXq, &dmean, &dcov, mean, cov, false)) return rc;
   if (int rc = stage_out_finish(h, dmean, mean, (size_t)G * q, where)) return rc;
   if (int rc = stage_out_finish(h, dcov, cov, (size_t)G * q * q, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
+
+}  // extern "C"
+
+namespace {
+
+// The group-chunk loop of the batch acquisition functions: d_info zeroed, then per chunk of at most `chunk` groups
+// `body(g0, gc)` (staging in, the kernels between the handle's two events, staging out), one synchronisation and the
+// events' elapsed time; at the end the breakdown report (info_finish with `not_pd`).  `report_ms`: last_ms / last_launches
+// become the sum of the chunks' event times and their count; otherwise they stay as the body left them.
+template <class Body>
+int for_group_chunks(tgp_handle h, int64_t G, int64_t chunk, bool report_ms, const char* not_pd, Body body) {
+  HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  double total_ms = 0.0;
+  int launches = 0;
+  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
+    const int64_t gc = std::min(chunk, G - g0);
+    if (int rc = body(g0, gc)) return rc;
+    if (int rc = sync(h)) return rc;
+    float ms = 0.f;
+    if (report_ms && hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;
+    ++launches;
+  }
+  if (report_ms) {
+    h->last_ms = total_ms;
+    h->last_launches = launches;
+  }
+  return info_finish(h, not_pd);
+}
+
+// ... with the joint posterior of each chunk's groups (joint_common into device scratch: the events bracket the posterior
+// part) in front of `tail(dmean, dcov, gc, dout)`, which writes `per_group` doubles per group towards `out`
+template <class Tail>
+int joint_tail_chunks(tgp_handle h, const double* Xq, int64_t G, int q, int64_t chunk, double* out, size_t per_group, int where,
+                      bool report_ms, const char* not_pd, Tail tail) {
+  return for_group_chunks(h, G, chunk, report_ms, not_pd, [&](int64_t g0, int64_t gc) -> int {
+    const double* dXq;
+    double *dmean, *dcov, *dout;
+    if (int rc = joint_common(h, Xq + g0 * q * h->d, gc, q, where, &dXq, &dmean, &dcov, nullptr, nullptr, true)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_out3, out + g0 * per_group, (size_t)gc * per_group, where, &dout)) return rc;
+    tail(dmean, dcov, gc, dout);
+    return stage_out_finish(h, dout, out + g0 * per_group, (size_t)gc * per_group, where);
+  });
+}
+
+}  // namespace
+
+extern "C" {
 
 int tgp_qei(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S, double eta,
             double jitter, double* out, int where) {
@@ -2458,38 +2518,15 @@ int tgp_qei(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps,
   if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
   if (G == 0) return TGP_OK;
   if (!out) return fail(h, TGP_ERR_ARG, "out is NULL");
-  const double* dXq;
-  double *dmean, *dcov;
   // chunk the groups so the [G,q,q] covariances stay within a bounded scratch (<= ~1 GiB)
   const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
   if (int rc = set_device(h)) return rc;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
-  double total_ms = 0.0;
-  int launches = 0;
-  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
-    const int64_t gc = std::min(chunk, G - g0);
-    if (int rc = joint_common(h, Xq + g0 * q * h->d, gc, q, where, &dXq, &dmean, &dcov, nullptr, nullptr, true))
-      return rc;
-    double* dout;
-    if (int rc = stage_out_prepare(h, h->s_out3, out + g0, gc, where, &dout)) return rc;
-    launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, eta, jitter, dout, nullptr, h->d_info.as<int>());
-    if (int rc = stage_out_finish(h, dout, out + g0, gc, where)) return rc;
-    if (int rc = sync(h)) return rc;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;
-    ++launches;
-  }
-  h->last_ms = total_ms;
-  h->last_launches = launches;
-  int info = 0;
-  HIPCHK(h, hipMemcpy(&info, h->d_info.p, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(h, hipGetLastError());
-  if (info != 0)
-    return fail(h, TGP_ERR_NOT_PD, "qEI: cov + jitter*I not positive definite for group %d", info - 1);
-  return TGP_OK;
+  return joint_tail_chunks(h, Xq, G, q, chunk, out, 1, where, true, QEI_NOT_PD,
+                           [&](const double* dmean, const double* dcov, int64_t gc, double* dout) {
+                             launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, eta, jitter, dout, nullptr, h->d_info.as<int>());
+                           });
 }
 
 // ---- analytic batch EI: tgp_qei's body with bei_tail_kernel behind the joint posterior -----------------------------------------
@@ -2515,15 +2552,6 @@ static int bei_stage_points(tgp_handle h, int q, const double* w1, const double*
   *d2 = p + n1;
   return TGP_OK;
 }
-static int bei_finish(tgp_handle h) {
-  int info = 0;
-  HIPCHK(h, hipMemcpy(&info, h->d_info.p, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(h, hipGetLastError());
-  if (info != 0)
-    return fail(h, TGP_ERR_NOT_PD, "batch EI: a covariance of group %d is not positive definite (after the 1e-6 jitters)",
-                info - 1);
-  return TGP_OK;
-}
 
 int tgp_batch_ei(tgp_handle h, const double* Xq, int64_t G, int q, const double* w1, const double* w2, int S, double eta,
                  double* out, int where) {
@@ -2531,32 +2559,15 @@ int tgp_batch_ei(tgp_handle h, const double* Xq, int64_t G, int q, const double*
   if (int rc = bei_check(h, q, w1, w2, S)) return rc;
   if (G == 0) return TGP_OK;
   if (!out) return fail(h, TGP_ERR_ARG, "out is NULL");
-  const double* dXq;
-  double *dmean, *dcov;
   const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));  // (tgp_qei's rule)
   if (int rc = set_device(h)) return rc;
   const double *dw1, *dw2;
   if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
-  double total_ms = 0.0;
-  int launches = 0;
-  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
-    const int64_t gc = std::min(chunk, G - g0);
-    if (int rc = joint_common(h, Xq + g0 * q * h->d, gc, q, where, &dXq, &dmean, &dcov, nullptr, nullptr, true))
-      return rc;
-    double* dout;
-    if (int rc = stage_out_prepare(h, h->s_out3, out + g0, gc, where, &dout)) return rc;
-    launch_bei_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, dout, h->d_info.as<int>());
-    if (int rc = stage_out_finish(h, dout, out + g0, gc, where)) return rc;
-    if (int rc = sync(h)) return rc;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;  // (the posterior part, as tgp_qei reports it)
-    ++launches;
-  }
-  h->last_ms = total_ms;
-  h->last_launches = launches;
-  return bei_finish(h);
+  // (the time reported is the posterior part, as tgp_qei reports it)
+  return joint_tail_chunks(h, Xq, G, q, chunk, out, 1, where, true, BEI_NOT_PD,
+                           [&](const double* dmean, const double* dcov, int64_t gc, double* dout) {
+                             launch_bei_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, dout, h->d_info.as<int>());
+                           });
 }
 
 int tgp_batch_ei_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* w1,
@@ -2566,31 +2577,20 @@ int tgp_batch_ei_moments(tgp_handle h, const double* mean, const double* cov, in
   if (G < 0 || (G > 0 && (!mean || !cov || !out))) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (G == 0) return TGP_OK;
   if (int rc = set_device(h)) return rc;
-  const double *dw1, *dw2, *dmean, *dcov;
+  const double *dw1, *dw2;
   if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
   const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
-  double total_ms = 0.0;
-  int launches = 0;
-  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
-    const int64_t gc = std::min(chunk, G - g0);
+  return for_group_chunks(h, G, chunk, true, BEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    const double *dmean, *dcov;
+    double* dout;
     if (int rc = stage_in(h, h->s_out1, mean + g0 * q, (size_t)gc * q, where, &dmean)) return rc;
     if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, (size_t)gc * q * q, where, &dcov)) return rc;
-    double* dout;
     if (int rc = stage_out_prepare(h, h->s_out3, out + g0, gc, where, &dout)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // here the events bracket the tail itself
     launch_bei_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, dout, h->d_info.as<int>());
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    if (int rc = stage_out_finish(h, dout, out + g0, gc, where)) return rc;
-    if (int rc = sync(h)) return rc;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;
-    ++launches;
-  }
-  h->last_ms = total_ms;
-  h->last_launches = launches;
-  return bei_finish(h);
+    return stage_out_finish(h, dout, out + g0, gc, where);
+  });
 }
 
 // ---- the analytic batch EI's gradient: bei_grad_tail_kernel on given moments, and tgp_qei_value_grad's body around it ---------------
@@ -2601,52 +2601,27 @@ int tgp_batch_ei_moments_grad(tgp_handle h, const double* mean, const double* co
   if (G < 0 || (G > 0 && (!mean || !cov || !val || !gmean || !gcov))) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (G == 0) return TGP_OK;
   if (int rc = set_device(h)) return rc;
-  const double *dw1, *dw2, *dmean, *dcov;
+  const double *dw1, *dw2;
   if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
   const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)q * q * 8));
-  double total_ms = 0.0;
-  int launches = 0;
-  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
-    const int64_t gc = std::min(chunk, G - g0);
-    // host residency: one staging buffer for the inputs (mean, cov), one for the outputs (val, gmean, gcov)
+  return for_group_chunks(h, G, chunk, true, BEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    // host residency: the moments through s_out1 / s_out2 as in tgp_batch_ei_moments, the value through s_out3, the two
+    // adjoints through s_in and s_ent (idle in a call on given moments: no candidates, no entropy tail)
+    const size_t nm = (size_t)gc * q, nc = (size_t)gc * q * q;
+    const double *dmean, *dcov;
     double *dval, *dgm, *dgc;
-    if (where == TGP_DEVICE) {
-      dmean = mean + g0 * q;
-      dcov = cov + g0 * q * q;
-      dval = val + g0;
-      dgm = gmean + g0 * q;
-      dgc = gcov + g0 * q * q;
-    } else {
-      HIPCHK(h, h->s_out1.reserve((size_t)gc * (q + q * q) * sizeof(double)));
-      HIPCHK(h, h->s_out2.reserve((size_t)gc * (1 + q + q * q) * sizeof(double)));
-      double* const in = h->s_out1.as<double>();
-      HIPCHK(h, hipMemcpyAsync(in, mean + g0 * q, (size_t)gc * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(in + gc * q, cov + g0 * q * q, (size_t)gc * q * q * sizeof(double), hipMemcpyHostToDevice,
-                               h->stream));
-      dmean = in;
-      dcov = in + gc * q;
-      dval = h->s_out2.as<double>();
-      dgm = dval + gc;
-      dgc = dgm + gc * q;
-    }
+    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, nm, where, &dmean)) return rc;
+    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, nc, where, &dcov)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_out3, val + g0, (size_t)gc, where, &dval)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_in, gmean + g0 * q, nm, where, &dgm)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_ent, gcov + g0 * q * q, nc, where, &dgc)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // the events bracket the tail itself
     launch_bei_grad_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, 0, dval, dgm, dgc, h->d_info.as<int>());
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    if (where != TGP_DEVICE) {
-      HIPCHK(h, hipMemcpyAsync(val + g0, dval, (size_t)gc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(gmean + g0 * q, dgm, (size_t)gc * q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(gcov + g0 * q * q, dgc, (size_t)gc * q * q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    if (int rc = sync(h)) return rc;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;
-    ++launches;
-  }
-  h->last_ms = total_ms;
-  h->last_launches = launches;
-  return bei_finish(h);
+    if (int rc = stage_out_finish(h, dval, val + g0, (size_t)gc, where)) return rc;
+    if (int rc = stage_out_finish(h, dgm, gmean + g0 * q, nm, where)) return rc;
+    return stage_out_finish(h, dgc, gcov + g0 * q * q, nc, where);
+  });
 }
 
 // K*^T, W K*, Gram product, pick, the tail with its moment adjoints, mix, the A product, joint_vjp_tail: one synchronisation.
@@ -2658,43 +2633,12 @@ int tgp_batch_ei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, co
   const double* dXq;
   int64_t P, Ppad;
   if (int rc = joint_small_common(h, Xq, G, q, where, &dXq, &P, &Ppad)) return rc;
-  const int64_t Npad = h->Npad;
   const double *dw1, *dw2;
-  double *dval, *dgrad;
   if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)P * h->d, where, &dgrad)) return rc;
-  const size_t part_doubles = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, h->dp));
-  HIPCHK(h, h->s_grad.reserve(((size_t)4 * Npad * Ppad + (size_t)Ppad * Ppad + part_doubles + (size_t)2 * P * (1 + q)) * sizeof(double)));
-  double* B = h->s_grad.as<double>();
-  double* C1 = B + (size_t)Npad * Ppad;
-  double* T1 = C1 + (size_t)Npad * Ppad;   // C1^T, then D
-  double* Z = T1 + (size_t)Npad * Ppad;
-  double* Spp = Z + (size_t)Npad * Ppad;
-  double* part = Spp + (size_t)Ppad * Ppad;
-  double* dmean = part + part_doubles;
-  double* dcov = dmean + P;
-  double* dgm = dcov + (size_t)P * q;
-  double* dgc = dgm + P;
-  const ModelDev m = model_dev(h);
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
-  launch_kstar_t(h->stream, m, dXq, P, Ppad, B);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B, Ppad, 0.0, C1, Ppad, 3))
-    return rc;
-  launch_transpose(h->stream, C1, Npad, Ppad, Ppad, T1, Npad);
-  if (int rc = gemm_tall(h, false, (int)Ppad, (int)Ppad, (int)Npad, 1.0, T1, Npad, C1, Ppad, 0.0, Spp, Ppad, 0)) return rc;
-  launch_predict_small_tail(h->stream, m, P, Ppad, B, C1, part, dmean, nullptr);
-  launch_joint_pick(h->stream, m, dXq, P, Ppad, q, Spp, dcov);
-  launch_bei_grad_tail(h->stream, dmean, dcov, G, q, dw1, dw2, S, eta, 1, dval, dgm, dgc, h->d_info.as<int>());
-  launch_joint_mix(h->stream, C1, dgc, P, Ppad, Npad, q, T1);
-  if (int rc = gemm_tall(h, false, (int)Npad, (int)Ppad, (int)Npad, 1.0, h->d_A.as<double>(), Npad, T1, Ppad, 0.0, Z, Ppad, 5))
-    return rc;
-  launch_joint_vjp_tail(h->stream, m, dXq, P, Ppad, q, B, C1, Z, part, dgm, dgc, dgrad);
-  if (int rc = stage_out_finish(h, dval, val, (size_t)G, where)) return rc;
-  if (int rc = stage_out_finish(h, dgrad, grad, (size_t)P * h->d, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  return bei_finish(h);
+  return joint_value_grad(h, dXq, G, q, P, Ppad, val, grad, where, BEI_NOT_PD,
+                          [&](const double* dmean, const double* dcov, double* dval, double* dgm, double* dgc) {
+                            launch_bei_grad_tail(h->stream, dmean, dcov, G, q, dw1, dw2, S, eta, 1, dval, dgm, dgc, h->d_info.as<int>());
+                          });
 }
 
 int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S,
@@ -2704,30 +2648,15 @@ int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const 
   if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
   if (G == 0) return TGP_OK;
   if (!out) return fail(h, TGP_ERR_ARG, "out is NULL");
-  const double* dXq;
-  double *dmean, *dcov;
   const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)q * std::max(q, S) * 8));
   if (int rc = set_device(h)) return rc;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
-  for (int64_t g0 = 0; g0 < G; g0 += chunk) {
-    const int64_t gc = std::min(chunk, G - g0);
-    if (int rc = joint_common(h, Xq + g0 * q * h->d, gc, q, where, &dXq, &dmean, &dcov, nullptr, nullptr, true))
-      return rc;
-    double* dout;
-    if (int rc = stage_out_prepare(h, h->s_out3, out + g0 * S * q, (size_t)gc * S * q, where, &dout)) return rc;
-    launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, 0.0, jitter, nullptr, dout, h->d_info.as<int>());
-    if (int rc = stage_out_finish(h, dout, out + g0 * S * q, (size_t)gc * S * q, where)) return rc;
-    if (int rc = sync(h)) return rc;
-  }
-  int info = 0;
-  HIPCHK(h, hipMemcpy(&info, h->d_info.p, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(h, hipGetLastError());
-  if (info != 0)
-    return fail(h, TGP_ERR_NOT_PD, "reparam samples: cov + jitter*I not positive definite for group %d", info - 1);
-  return TGP_OK;
+  return joint_tail_chunks(h, Xq, G, q, chunk, out, (size_t)S * q, where, false,
+                           "reparam samples: cov + jitter*I not positive definite for group %d",
+                           [&](const double* dmean, const double* dcov, int64_t gc, double* dout) {
+                             launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, 0.0, jitter, nullptr, dout, h->d_info.as<int>());
+                           });
 }
 
 // ---- trajectories -----------------------------------------------------------------------------
@@ -3012,9 +2941,7 @@ int tgp_traj_eval(tgp_traj t, const double* Xq, int64_t M, int per_traj_inputs, 
     launch_traj_eval(h->stream, traj_dev(t), dXq, M, per_traj_inputs, dout, nullptr, nullptr, 0);
   }
   if (int rc = stage_out_finish(h, dout, out, (size_t)M * t->B, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 int tgp_traj_value_grad(tgp_traj t, const double* Xq, int64_t P, double* val, double* grad, int where) {
@@ -3033,9 +2960,7 @@ int tgp_traj_value_grad(tgp_traj t, const double* Xq, int64_t P, double* val, do
   launch_traj_grad(h->stream, traj_dev(t), dXq, nitems, dval, dgrad);
   if (int rc = stage_out_finish(h, dval, val, (size_t)nitems, where)) return rc;
   if (int rc = stage_out_finish(h, dgrad, grad, (size_t)nitems * h->d, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 // arg-min of the B trajectories over device-resident candidates into DEVICE slots fv [B], fi [B]: enqueue only
@@ -3070,9 +2995,7 @@ int tgp_traj_argmin(tgp_traj t, const double* Xq, int64_t M, int64_t index_base,
   if (int rc = enqueue_traj_argmin(t, dXq, M, index_base, fv, fi)) return rc;
   if (best_val) HIPCHK(h, hipMemcpyAsync(best_val, fv, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx, fi, B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 int tgp_traj_argmin_async(tgp_traj t, const double* Xq_device, int64_t M, int64_t index_base, double* pairs_device) {
@@ -3092,9 +3015,7 @@ int tgp_traj_argmin_async(tgp_traj t, const double* Xq_device, int64_t M, int64_
 int tgp_stream_synchronize(tgp_handle h) {
   if (!h) return TGP_ERR_ARG;
   if (int rc = set_device(h)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
-  return TGP_OK;
+  return finish(h);
 }
 
 // the header words of the last pruned arg-max up to the range boundaries (tgp_internal.hpp PRUNE_W_*); zeros when none ran
@@ -3286,8 +3207,7 @@ int tgp_ehvi_moments(tgp_handle h, const double* mean, const double* var, int64_
   if (int rc = stage_out_prepare(h, h->s_out3, out, M, where, &dout)) return rc;
   if (int rc = ehvi_enqueue_tail(h, dmean, dvar, M, dout)) return rc;
   if (int rc = stage_out_finish(h, dout, out, M, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
+  if (int rc = finish(h)) return rc;
   ehvi_read_tail_ms(h);
   h->ehvi_sweep_ms = 0.0;
   h->last_ms = h->ehvi_tail_ms;
@@ -3307,8 +3227,7 @@ int tgp_ehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t M, do
   if (int rc = stage_out_prepare(h, h->s_out3, out, M, where, &dout)) return rc;
   if (int rc = ehvi_enqueue_tail(h, dmean, dvar, M, dout)) return rc;
   if (int rc = stage_out_finish(h, dout, out, M, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
+  if (int rc = finish(h)) return rc;
   ehvi_read_tail_ms(h);
   h->last_ms = h->ehvi_sweep_ms;
   h->last_launches = P;
@@ -3324,32 +3243,17 @@ int tgp_ehvi_argmax(const tgp_handle* hs, int P, const double* Xq, int64_t M, in
   double *dmean, *dvar;
   if (int rc = ehvi_stack_moments(hs, P, Xq, M, where, &dXq, &dmean, &dvar)) return rc;
   HIPCHK(h, h->s_out3.reserve((size_t)M * sizeof(double)));
-  HIPCHK(h, h->s_small.reserve(64));
+  Winner w;
+  if (int rc = w.slots(h)) return rc;
   double* dvals = h->s_out3.as<double>();
-  double* fv = h->s_small.as<double>();
-  int64_t* fi = (int64_t*)(fv + 1);
   if (int rc = ehvi_enqueue_tail(h, dmean, dvar, M, dvals)) return rc;
-  if (int rc = enqueue_topk_of_values(h, dvals, M, index_base, 1, fv, fi)) return rc;
-  double hv;
-  int64_t hi;
-  HIPCHK(h, hipMemcpyAsync(&hv, fv, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&hi, fi, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-  if (int rc = sync(h)) return rc;
-  HIPCHK(h, hipGetLastError());
+  if (int rc = enqueue_topk_of_values(h, dvals, M, index_base, 1, w.fv, w.fi)) return rc;
+  if (int rc = w.enqueue_read(h)) return rc;
+  if (int rc = finish(h)) return rc;
   ehvi_read_tail_ms(h);
   h->last_ms = h->ehvi_sweep_ms;
   h->last_launches = P;
-  if (best_val) *best_val = hv;
-  if (best_idx) *best_idx = hi;
-  if (best_x) {
-    const int64_t local = hi - index_base;
-    if (local < 0 || local >= M) return fail(h, TGP_ERR_HIP, "arg-max produced no valid index (all NaN?)");
-    if (where == TGP_DEVICE)
-      HIPCHK(h, hipMemcpy(best_x, dXq + local * h->d, h->d * sizeof(double), hipMemcpyDeviceToHost));
-    else
-      memcpy(best_x, Xq + local * h->d, h->d * sizeof(double));
-  }
-  return TGP_OK;
+  return w.give(h, Xq, dXq, M, index_base, where, best_val, best_idx, best_x);
 }
 
 int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms) {

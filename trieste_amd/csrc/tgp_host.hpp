@@ -58,6 +58,20 @@ struct DevBuf {  // grow-only device buffer
   T* as() const { return (T*)p; }
 };
 
+// The carving of one scratch buffer into `n` arrays of doubles, back to back in the order listed: offsets[i] is where
+// array i starts, the return value what the buffer must hold.  Pure arithmetic (tgp_api.hip `carve` reserves and hands
+// out the pointers from it).  Nothing is padded: an array sits on a multiple of 64 doubles whenever every array in
+// front of it has such a size -- the N x P and P x P arrays (Npad a multiple of 256, Ppad of 64) go first, the
+// partial-sum areas and the small moment arrays behind them.
+inline size_t scratch_offsets(const size_t* counts, int n, size_t* offsets) {
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    offsets[i] = total;
+    total += counts[i];
+  }
+  return total;
+}
+
 }  // namespace tgp
 
 using tgp::DevBuf;
