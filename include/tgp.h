@@ -267,8 +267,11 @@ int tgp_qei(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps,
  * Xq); out [G].  The reference's constants are built in: cov + 1e-6 I before the closed form (function.py:1776-1783), another
  * 1e-6 I inside every CDF's factorisation (utils.py:114, 143-144), 1e-12 on the factor's diagonal, the quantile's argument
  * kept in [1e-6, 1 - 1e-6] (utils.py:177).  The value is NOT clipped at zero.  2 <= q <= 16 (q = 1 is an error in the
- * reference as well: MultivariateNormalCDF(dim = 0)), S >= 1, else TGP_ERR_SHAPE / TGP_ERR_ARG; TGP_ERR_NOT_PD names the
- * first group one of whose factorisations met a non-positive pivot.  Value only; the gradient is behind
+ * reference as well: MultivariateNormalCDF(dim = 0)), S >= 1, else TGP_ERR_SHAPE / TGP_ERR_ARG; TGP_ERR_NOT_PD names a
+ * group one of whose factorisations met a non-positive pivot, by its index in the call.  The groups are walked in chunks of
+ * at most 2^30 / (8 q^2) (tgp_batch_ei_moments_grad: 2^28 / (8 q^2)) so that the covariances stay within a bounded scratch;
+ * the call ends at the first chunk that holds such a group and names one of that chunk's -- the only one, if there is only
+ * one; not necessarily the lowest.  tgp_qei and tgp_reparam_samples report the same way.  Value only; the gradient is behind
  * tgp_batch_ei_value_grad below.
  *   tgp_batch_ei_moments: the same tail on caller-supplied moments, mean [G,q] and cov [G,q,q] AS THE MODEL RETURNS THEM
  *     (the entry applies the 1e-6 and the change of sign itself); needs no data on the handle. */

@@ -116,15 +116,16 @@ int finish(tgp_handle h) {
   return TGP_OK;
 }
 
-constexpr const char* QEI_NOT_PD = "qEI: cov + jitter*I not positive definite for group %d";
-constexpr const char* BEI_NOT_PD = "batch EI: a covariance of group %d is not positive definite (after the 1e-6 jitters)";
+constexpr const char* QEI_NOT_PD = "qEI: cov + jitter*I not positive definite for group %lld";
+constexpr const char* BEI_NOT_PD = "batch EI: a covariance of group %lld is not positive definite (after the 1e-6 jitters)";
 // d_info after the stream has drained: the 1-based group a device factorisation broke down at -> TGP_ERR_NOT_PD with `fmt`
-// (one %d: the 0-based group), else the call's launch check
-int info_finish(tgp_handle h, const char* fmt) {
+// (one %lld: the 0-based group of the CALL -- the tails count within their launch, `g0` is the launch's first group), else the
+// call's launch check
+int info_finish(tgp_handle h, const char* fmt, int64_t g0 = 0) {
   int info = 0;
   HIPCHK(h, hipMemcpy(&info, h->d_info.p, sizeof(int), hipMemcpyDeviceToHost));
   HIPCHK(h, hipGetLastError());
-  if (info != 0) return fail(h, TGP_ERR_NOT_PD, fmt, info - 1);
+  if (info != 0) return fail(h, TGP_ERR_NOT_PD, fmt, (long long)(g0 + info - 1));
   return TGP_OK;
 }
 
@@ -2471,25 +2472,29 @@ namespace {
 // `body(g0, gc)` (staging in, the kernels between the handle's two events, staging out), one synchronisation and the
 // events' elapsed time; at the end the breakdown report (info_finish with `not_pd`).  `report_ms`: last_ms / last_launches
 // become the sum of the chunks' event times and their count; otherwise they stay as the body left them.
+// The tails report a group by its index within their launch, and the word keeps the first report: a call of more than one
+// chunk reads it behind every chunk's synchronisation, while the chunk's base is known, and ends at the first chunk that broke
+// down (the chunks after it are not computed).  One read per chunk: a call of one chunk reads it once, at the end, as before.
 template <class Body>
 int for_group_chunks(tgp_handle h, int64_t G, int64_t chunk, bool report_ms, const char* not_pd, Body body) {
   HIPCHK(h, h->d_info.reserve(sizeof(int)));
   HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
   double total_ms = 0.0;
-  int launches = 0;
+  int launches = 0, rc = TGP_OK;
   for (int64_t g0 = 0; g0 < G; g0 += chunk) {
     const int64_t gc = std::min(chunk, G - g0);
-    if (int rc = body(g0, gc)) return rc;
-    if (int rc = sync(h)) return rc;
+    if (int rb = body(g0, gc)) return rb;
+    if (int rs = sync(h)) return rs;
     float ms = 0.f;
     if (report_ms && hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) total_ms += ms;
     ++launches;
+    if ((rc = info_finish(h, not_pd, g0))) break;
   }
   if (report_ms) {
     h->last_ms = total_ms;
     h->last_launches = launches;
   }
-  return info_finish(h, not_pd);
+  return rc;
 }
 
 // ... with the joint posterior of each chunk's groups (joint_common into device scratch: the events bracket the posterior
@@ -2653,7 +2658,7 @@ int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const 
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
   return joint_tail_chunks(h, Xq, G, q, chunk, out, (size_t)S * q, where, false,
-                           "reparam samples: cov + jitter*I not positive definite for group %d",
+                           "reparam samples: cov + jitter*I not positive definite for group %lld",
                            [&](const double* dmean, const double* dcov, int64_t gc, double* dout) {
                              launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, 0.0, jitter, nullptr, dout, h->d_info.as<int>());
                            });
