@@ -386,6 +386,9 @@ int tgp_sample_joint(tgp_handle h, const double* Xq, int64_t n, const double* ep
  * RandomFourierFeaturesCosine), w [F,B] (prior weights), xi [N,B] (noise draws).
  * v = (K + noise I)^-1 ((Y - c) + sqrt(noise) xi - Phi_Z w) is computed from the CACHED factor
  * (the reference re-factorises per trajectory, sampler.py:730).  All inputs HOST.
+ * Any B >= 1 (both kinds): tgp_traj_eval with per-trajectory inputs and tgp_traj_value_grad serve every B; tgp_traj_eval
+ * with shared inputs, tgp_traj_argmin and tgp_traj_argmin_async hold one accumulator per trajectory in a thread and return
+ * TGP_ERR_SHAPE for B > 16.
  *
  * A trajectory BELONGS TO THE FACTORISATION IT WAS DRAWN FROM (both kinds): its weights are solved for -- and sized by --
  * the N, inputs and hyper-parameters of the handle at creation, and its kernels read the handle's model.  Once that model

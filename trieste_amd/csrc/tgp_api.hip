@@ -2746,10 +2746,29 @@ int tgp_traj_create(tgp_handle h, const double* rff_W, const double* rff_b, int 
   // Phi_Z w  -> s_out1 [N][B]
   TCHK(h->s_out1.reserve((size_t)N * B * sizeof(double)));
   TrajDev td = traj_dev(t);
-  launch_rff_project(h->stream, td, h->d_X.as<double>(), N, h->s_out1.as<double>());
-  std::vector<double> proj((size_t)N * B);
-  TCHK(hipMemcpyAsync(proj.data(), h->s_out1.p, proj.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  TCHK(hipStreamSynchronize(h->stream));
+  // the shared-input kernel holds at most 16 columns per thread (launch_traj_bp: for B > 16 its masked form would write
+  // columns 0..15 only): a wider set is projected in groups of up to 16 columns, each a trajectory set of its own over a
+  // packed copy of its weights.  A column's fused multiply-adds run in the same order in every form, so it keeps the bits
+  // it has alone.
+  std::vector<double> proj((size_t)N * B), wsg, pg((size_t)N * std::min(B, 16));
+  for (int b0 = 0; b0 < B; b0 += 16) {
+    const int gb = std::min(16, B - b0);
+    TrajDev tg = td;
+    if (gb < B) {
+      wsg.resize((size_t)F * gb);
+      for (int f = 0; f < F; ++f)
+        for (int b = 0; b < gb; ++b) wsg[(size_t)f * gb + b] = ws[(size_t)f * B + b0 + b];
+      TCHK(h->s_in.reserve((size_t)F * 16 * sizeof(double)));
+      TCHK(hipMemcpyAsync(h->s_in.p, wsg.data(), wsg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      tg.B = gb;
+      tg.ws = h->s_in.as<double>();
+    }
+    launch_rff_project(h->stream, tg, h->d_X.as<double>(), N, h->s_out1.as<double>());
+    TCHK(hipMemcpyAsync(pg.data(), h->s_out1.p, (size_t)N * gb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    TCHK(hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < N; ++i)
+      for (int b = 0; b < gb; ++b) proj[(size_t)i * B + b0 + b] = pg[(size_t)i * gb + b];
+  }
   // per trajectory: diff_b (padded) -> tmp1 ; tmp2 = W diff ; v_b = Wt tmp2
   const double sn = std::sqrt(h->noise);
   std::vector<double> diff((size_t)Npad, 0.0), vhost((size_t)Npad * B, 0.0), vb((size_t)Npad);

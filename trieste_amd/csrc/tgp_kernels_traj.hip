@@ -212,7 +212,8 @@ static void launch_traj_any(hipStream_t s, const TrajDev& t, const double* Xq, i
 int64_t traj_grid(int64_t M) { return (M + 255) / 256; }
 
 // out[M][B] = sum_k k(x, X_k) v[k][b] for B <= 16 weight vectors over the model's training inputs (t.F must be 0):
-// the m = rank-of-the-update dot products GIBBON's conditioned variance needs per candidate.
+// the m = rank-of-the-update dot products GIBBON's conditioned variance needs per candidate (prepare_repulsion takes the
+// low-rank path for m <= 16 only: the masked 16-column form writes no column beyond that).
 void launch_kernel_sums(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, double* out) {
   launch_traj_any(s, t, Xq, M, 0, 3, out, nullptr, nullptr, 0);
 }
@@ -316,7 +317,7 @@ void launch_rff_features(hipStream_t s, const TrajDev& t, double scale, int64_t 
 }
 
 // Phi_Z w at a set of RAW points (the training inputs): out [npts][B] = sum_f phi_f(x) ws[f][b]
-// (sampler.py:726 `phi_Z @ prior_weights`).
+// (sampler.py:726 `phi_Z @ prior_weights`).  The shared-input form: t.B <= 16 (tgp_traj_create hands wider sets over in groups).
 void launch_rff_project(hipStream_t s, const TrajDev& t, const double* X_raw, int64_t npts, double* out) {
   launch_traj_any(s, t, X_raw, npts, 0, 1, out, nullptr, nullptr, 0);
 }
