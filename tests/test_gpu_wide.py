@@ -312,6 +312,32 @@ def test_wide_cov_between_clone_and_append(cfg):
     assert_close(m0, om, atol=floor * 10, what="original mean")
 
 
+def test_wide_gibbon_with_a_repulsion_twin_of_a_few_appended_rows_sweeps_the_twin():
+    """A twin that is this model + m <= 16 rows takes the rank-m form (kernel sums of the trajectory kernel) at d <= 32.  That
+    kernel has no wide instantiation: at d = 33 the twin is swept, and GIBBON equals the oracle's block-determinant form at
+    the tolerances of test_gpu_parity.py's rank-m test.  (Before the launchers refused a padded dimension they are not compiled
+    for, this case ran the dp = 32 instantiation over rows of 64 coordinates and returned numbers.)"""
+    _, obj, d, kind, N, noise = CONFIGS[0]
+    X, Y, ls, c, st, Xq = _problem(obj, d, kind, N, noise, M=1200)
+    floor = cancellation_floor(N, 1.0, noise)
+    rng = np.random.default_rng(17)
+    samples = O.eta_min_mean(st) - np.array([0.02, 0.1, 0.3])
+    om, ov = O.predict(st, Xq)
+    gmax = np.max((samples[None, :] - om[:, None]) / np.sqrt(ov)[:, None], axis=1)
+    ok = gmax <= 30.0
+    m = 3
+    pending = rng.uniform(size=(m, d))
+    eng = _engine(kind, d, 1.0, ls, noise, c, X, Y)
+    eng.set_min_value_samples(samples)
+    twin = eng.clone()
+    twin.append_data(pending, rng.standard_normal(m))  # observations do not matter
+    eng.set_repulsion(twin, 1.0 / m ** 2)
+    vals = eng.acq_values("gibbon", 0.0, Xq)
+    ref = O.gibbon_quality_term(om, ov, samples, noise) + O.gibbon_repulsion_term(st, Xq, pending, True)
+    sens = floor * 10 * (1.0 + np.abs(gmax)) / np.sqrt(ov) + floor / noise + 1e-13
+    assert_close(vals[ok], ref[ok], rtol=1e-6, atol=sens[ok], what="wide GIBBON with a rank-3 twin == reference form")
+
+
 @pytest.mark.parametrize("kind", ["soft", "hard"])
 def test_wide_penalized_values_and_gradient_match_oracle(kind):
     """Local penalization at d = 64 (the penalty kernels loop over the coordinates: no MAX_D-sized locals)."""

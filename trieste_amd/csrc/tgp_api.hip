@@ -941,7 +941,7 @@ int joint_backward(tgp_handle h, const JointScratch& w, const double* dXq, int64
                    const double* dgc, double* dgrad) {
   launch_joint_mix(h->stream, w.C1, dgc, P, Ppad, h->Npad, q, w.T);
   if (int rc = wt_product(h, h->d_A.as<double>(), h->Npad, w.T, Ppad, w.Z)) return rc;
-  launch_joint_vjp_tail(h->stream, model_dev(h), dXq, P, Ppad, q, w.B, w.C1, w.Z, w.part, dgm, dgc, dgrad);
+  HIPCHK(h, launch_joint_vjp_tail(h->stream, model_dev(h), dXq, P, Ppad, q, w.B, w.C1, w.Z, w.part, dgm, dgc, dgrad));
   return TGP_OK;
 }
 // Value [G] and gradient [P][d] of a batch acquisition function over G groups of q resident points in ONE call, everything on
@@ -972,7 +972,8 @@ constexpr int ACQ_LOGYVAR = 6;  // internal tail log(var + noise): tgp::ACQ_LOGY
 
 // Is the repulsion twin this model + m <= 16 appended rows with equal hyper-parameters?  Then (see
 // lowrank_var_kernel) its variance needs m kernel sums per candidate instead of a second sweep.  The answer and
-// the weight columns are cached per (this model's data, the twin's data) version pair.
+// the weight columns are cached per (this model's data, the twin's data) version pair.  Wide models (dp > MAX_D) sweep the
+// twin: the kernel sums are a form of the trajectory kernel, which has no wide instantiation.
 int prepare_repulsion(tgp_handle h) {
   tgp_handle t = h->rep_twin;
   if (h->rep_checked && h->rep_self_version == h->data_version && h->rep_twin_version == t->data_version)
@@ -981,7 +982,8 @@ int prepare_repulsion(tgp_handle h) {
   h->rep_lowrank = false;
   const int64_t m = t->N - h->N;
   const bool no_lowrank = getenv("TGP_NO_LOWRANK") != nullptr;  // A/B aid (read per check: tests toggle it)
-  bool ok = !no_lowrank && m >= 1 && m <= 16 && t->variance == h->variance && t->noise == h->noise && t->ls == h->ls;
+  bool ok = !no_lowrank && h->dp <= MAX_D && m >= 1 && m <= 16 && t->variance == h->variance && t->noise == h->noise &&
+            t->ls == h->ls;
   if (ok) {
     HIPCHK(h, h->s_small.reserve(64));
     int* flag = h->s_small.as<int>();
@@ -1043,7 +1045,7 @@ int acq_values_device(tgp_handle h, int acq_kind, double param, const double* dX
         tr.B = m;
         tr.v = h->d_repv.as<double>();
         tr.canonical = 1;
-        launch_kernel_sums(h->stream, tr, dXq, M, h->s_ks.as<double>());
+        HIPCHK(h, launch_kernel_sums(h->stream, tr, dXq, M, h->s_ks.as<double>()));
         launch_lowrank_var(h->stream, var, h->s_ks.as<double>(), M, m, var_twin);
       } else {  // any other twin: its own variance sweep
         SweepArgs b{};
@@ -1348,7 +1350,7 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
   launch_scale_inputs(s, h->d_X.as<double>(), h->d_ls.as<double>(), h->d_Xs.as<double>(), N, Npad, d, dp);
   launch_centred_rows(s, h->d_Xs.as<double>(), h->d_xc.as<double>(), h->d_xn.as<double>(), Npad, dp);
   if (keep_rows == 0) {
-    launch_assemble_K(s, h->d_Xs.as<double>(), A, N, Npad, dp, h->kind, h->variance, h->noise);
+    HIPCHK(h, launch_assemble_K(s, h->d_Xs.as<double>(), A, N, Npad, dp, h->kind, h->variance, h->noise));
     if (h->zeroed_L != L || h->zeroed_W != W || h->zeroed_npad != Npad) {
       HIPCHK(h, hipMemsetAsync(L, 0, nn, s));
       HIPCHK(h, hipMemsetAsync(W, 0, nn, s));
@@ -1378,7 +1380,7 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
     // rows [lo, Npad) of K + noise I in a scratch strip addressed with global row indices (d_A holds Wt)
     HIPCHK(h, h->s_grad.reserve((size_t)s2 * Npad * sizeof(double)));
     double* As = h->s_grad.as<double>() - (size_t)lo * Npad;
-    launch_assemble_K(s, h->d_Xs.as<double>(), As, N, Npad, dp, h->kind, h->variance, h->noise, lo);
+    HIPCHK(h, launch_assemble_K(s, h->d_Xs.as<double>(), As, N, Npad, dp, h->kind, h->variance, h->noise, lo));
     if (h->zeroed_L != L || h->zeroed_W != W || h->zeroed_npad != Npad) {  // (cannot happen: the append path keeps its buffers)
       HIPCHK(h, hipMemsetAsync(L + (size_t)lo * Npad, 0, (size_t)s2 * Npad * sizeof(double), s));
       HIPCHK(h, hipMemsetAsync(W + (size_t)lo * Npad, 0, (size_t)s2 * Npad * sizeof(double), s));
@@ -1506,7 +1508,7 @@ static int nlml_trial_enqueue(tgp_handle h, BatchScratch& bs, int B, double* sma
   // every member's scaled inputs / centred targets, then every member's K + noise I: two launches for the group (the
   // per-member scalars -- variance, noise, mean: slots 32 .. 34 of the member's block -- were uploaded with the call)
   launch_batch_prep(s, h->d_X.as<double>(), h->d_Y.as<double>(), small, (int64_t)small_per, B, Xs_all, errs, N, Npad, d, dp);
-  launch_assemble_K_batch(s, Xs_all, mats, N, Npad, dp, h->kind, small, (int64_t)small_per, (int64_t)(3 * nn), B);
+  HIPCHK(h, launch_assemble_K_batch(s, Xs_all, mats, N, Npad, dp, h->kind, small, (int64_t)small_per, (int64_t)(3 * nn), B));
   static const bool timing = getenv("TGP_TIMING") != nullptr;  // development aid: where a batched launch spends its time
   hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
   if (timing) {
@@ -1929,7 +1931,7 @@ int tgp_nlml(tgp_handle h, double* value, double* grad) {
     // [tm T, N) shrinks with the tile row, so the row-by-row order of the live-tile grid is longest-first
     launch_gemm(h->stream, false, (int)Npad, (int)Npad, (int)Npad, 1.0, h->d_A.as<double>(), Npad, h->d_W.as<double>(),
                 Npad, 0.0, Kinv, Npad, true, 4, Npad <= 4096 ? 1 : 0);
-    launch_nlml(h->stream, model_dev(h), Kinv, h->d_L.as<double>(), h->d_err.as<double>(), h->s_blkv.as<double>(), out);
+    HIPCHK(h, launch_nlml(h->stream, model_dev(h), Kinv, h->d_L.as<double>(), h->d_err.as<double>(), h->s_blkv.as<double>(), out));
   } else {  // value only: 1/2 err^T alpha + sum log L_ii + N/2 log(2 pi)
     launch_nlml_value(h->stream, model_dev(h), h->d_L.as<double>(), h->d_err.as<double>(), out);
   }
@@ -2035,7 +2037,7 @@ int tgp_predict_mean(tgp_handle h, const double* Xq, int64_t M, double* mean, in
   double* dmean;
   if (int rc = stage_in(h, h->s_in, Xq, (size_t)M * h->d, where, &dXq)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, mean, M, where, &dmean)) return rc;
-  launch_predict_mean(h->stream, model_dev(h), dXq, M, dmean);
+  HIPCHK(h, launch_predict_mean(h->stream, model_dev(h), dXq, M, dmean));
   if (int rc = stage_out_finish(h, dmean, mean, M, where)) return rc;
   return finish(h);
 }
@@ -2046,7 +2048,7 @@ int tgp_eta(tgp_handle h, double* eta) {
   if (int rc = set_device(h)) return rc;
   HIPCHK(h, h->s_out1.reserve(h->N * sizeof(double)));
   HIPCHK(h, h->s_small.reserve(64));
-  launch_predict_mean(h->stream, model_dev(h), h->d_X.as<double>(), h->N, h->s_out1.as<double>());
+  HIPCHK(h, launch_predict_mean(h->stream, model_dev(h), h->d_X.as<double>(), h->N, h->s_out1.as<double>()));
   launch_min_value(h->stream, h->s_out1.as<double>(), h->N, h->s_small.as<double>());
   HIPCHK(h, hipMemcpyAsync(eta, h->s_small.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   return finish(h);
@@ -2101,7 +2103,7 @@ int tgp_acq_value_grad(tgp_handle h, int acq_kind, double param, const double* X
     const ModelDev m = model_dev(t);
     if (int rc = kstar_products(h, m, t->d_W.as<double>(), t->Npad, dXq, P, Ppad, B, C1)) return rc;
     if (int rc = wt_product(h, t->d_A.as<double>(), t->Npad, C1, Ppad, Z)) return rc;
-    launch_grad_tail(h->stream, m, dXq, P, Ppad, B, C1, Z, gpart, kind, par, dval, dgrad, samples, S, rep_w, accum);
+    HIPCHK(h, launch_grad_tail(h->stream, m, dXq, P, Ppad, B, C1, Z, gpart, kind, par, dval, dgrad, samples, S, rep_w, accum));
     return TGP_OK;
   };
   if (int rc = pass(h, acq_kind, param, h->d_ent.as<double>(), h->ent_S, twin ? h->rep_weight : 0.0, 0.0)) return rc;
@@ -2253,7 +2255,7 @@ int tgp_sample_joint(tgp_handle h, const double* Xq, int64_t n, const double* ep
   const ModelDev m = model_dev(h);
   hipStream_t s = h->stream;
   HIPCHK(h, hipMemsetAsync(info, 0, sizeof(int), s));
-  launch_predict_mean(s, m, dXq, n, mean);
+  HIPCHK(h, launch_predict_mean(s, m, dXq, n, mean));
   // cov = k(Xq, Xq) - (W k(X, Xq))^T (W k(X, Xq)) + jitter I   (gpflow predict_f(full_cov) + sample_mvn)
   launch_kstar_t(s, m, dXq, n, Pp, B1);
   launch_gemm(s, false, (int)Npad, (int)Pp, (int)Npad, 1.0, h->d_W.as<double>(), Npad, B1, Pp, 0.0, C1, Pp, false, 3);
@@ -2763,7 +2765,7 @@ int tgp_traj_create(tgp_handle h, const double* rff_W, const double* rff_b, int 
       tg.B = gb;
       tg.ws = h->s_in.as<double>();
     }
-    launch_rff_project(h->stream, tg, h->d_X.as<double>(), N, h->s_out1.as<double>());
+    TCHK(launch_rff_project(h->stream, tg, h->d_X.as<double>(), N, h->s_out1.as<double>()));
     TCHK(hipMemcpyAsync(pg.data(), h->s_out1.p, (size_t)N * gb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     TCHK(hipStreamSynchronize(h->stream));
     for (int64_t i = 0; i < N; ++i)
@@ -2962,7 +2964,7 @@ int tgp_traj_eval(tgp_traj t, const double* Xq, int64_t M, int per_traj_inputs, 
   if (int rc = stage_out_prepare(h, h->s_out1, out, (size_t)M * t->B, where, &dout)) return rc;
   {
     TimedLaunch timed(h);
-    launch_traj_eval(h->stream, traj_dev(t), dXq, M, per_traj_inputs, dout, nullptr, nullptr, 0);
+    HIPCHK(h, launch_traj_eval(h->stream, traj_dev(t), dXq, M, per_traj_inputs, dout, nullptr, nullptr, 0));
   }
   if (int rc = stage_out_finish(h, dout, out, (size_t)M * t->B, where)) return rc;
   return finish(h);
@@ -2981,7 +2983,7 @@ int tgp_traj_value_grad(tgp_traj t, const double* Xq, int64_t P, double* val, do
   if (int rc = stage_in(h, h->s_in, Xq, (size_t)nitems * h->d, where, &dXq)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)nitems, where, &dval)) return rc;
   if (int rc = stage_out_prepare(h, h->s_out2, grad, (size_t)nitems * h->d, where, &dgrad)) return rc;
-  launch_traj_grad(h->stream, traj_dev(t), dXq, nitems, dval, dgrad);
+  HIPCHK(h, launch_traj_grad(h->stream, traj_dev(t), dXq, nitems, dval, dgrad));
   if (int rc = stage_out_finish(h, dval, val, (size_t)nitems, where)) return rc;
   if (int rc = stage_out_finish(h, dgrad, grad, (size_t)nitems * h->d, where)) return rc;
   return finish(h);
@@ -2996,7 +2998,8 @@ static int enqueue_traj_argmin(tgp_traj t, const double* dXq, int64_t M, int64_t
   HIPCHK(h, h->s_blki.reserve((size_t)grid * B * sizeof(int64_t)));
   {
     TimedLaunch timed(h);
-    launch_traj_eval(h->stream, traj_dev(t), dXq, M, 0, nullptr, h->s_blkv.as<double>(), h->s_blki.as<int64_t>(), index_base);
+    HIPCHK(h, launch_traj_eval(h->stream, traj_dev(t), dXq, M, 0, nullptr, h->s_blkv.as<double>(), h->s_blki.as<int64_t>(),
+                               index_base));
   }
   launch_argmin_final_multi(h->stream, h->s_blkv.as<double>(), h->s_blki.as<int64_t>(), grid, B, fv, fi);
   return TGP_OK;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <vector>
 
 namespace tgp {
@@ -17,14 +18,43 @@ constexpr int DP_WIDE = 0;       // template argument of the wide instantiations
 constexpr int TRIAL_WIDE_LS = 48;  // batched trials at dp > MAX_D: a member's lengthscales sit at [48, 48 + dp) of its hyper block
 constexpr int MAX_Q = 64;
 
+// The narrow padded dimensions, ascending up to MAX_D: the DP the register-resident kernels are compiled for.  DESIGN.md 4.7
+// has the table of which launcher family covers which of them.
+inline constexpr int NARROW_DP[] = {2, 4, 6, 8, 16, 32};
+constexpr int N_NARROW_DP = sizeof(NARROW_DP) / sizeof(NARROW_DP[0]);
+static_assert(NARROW_DP[N_NARROW_DP - 1] == MAX_D, "the list ends at MAX_D");
+
 inline int dpad_of(int d) {
-  if (d <= 2) return 2;
-  if (d <= 4) return 4;
-  if (d <= 6) return 6;
-  if (d <= 8) return 8;
-  if (d <= 16) return 16;
-  if (d <= 32) return 32;
+  for (int dp : NARROW_DP)
+    if (d <= dp) return dp;
   return (d + WIDE_CHUNK - 1) / WIDE_CHUNK * WIDE_CHUNK;
+}
+
+// The one step from a run-time padded dimension to an instantiation: f(std::integral_constant<int, DP>{}) for the DP of
+// NARROW_DP that equals dp and is <= MAXDP (what the caller's kernel family is compiled for: 16 or 32); its hipError_t is the
+// result.  Any other dp -- wide inputs, which a caller branches off in front of this, included -- is hipErrorInvalidValue and
+// f is not called.  f is not instantiated for the entries above MAXDP.
+template <int MAXDP, int I = 0, typename F>
+inline hipError_t with_dp(int dp, F&& f) {
+  static_assert(MAXDP == 16 || MAXDP == MAX_D, "a family is compiled up to 16 or up to MAX_D");
+  if constexpr (I < N_NARROW_DP) {
+    if constexpr (NARROW_DP[I] <= MAXDP) {
+      if (dp == NARROW_DP[I]) return f(std::integral_constant<int, NARROW_DP[I]>{});
+    }
+    return with_dp<MAXDP, I + 1>(dp, f);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+// The same for the kernel kind, by_kind's convention: 0, 1, 2, and anything else is kind 3.  The result is f's.
+template <typename F>
+inline auto with_kind(int kind, F&& f) {
+  switch (kind) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
+  }
 }
 
 struct ModelDev {       // device-resident model state (all pointers device)
@@ -163,10 +193,10 @@ void launch_sweep_combine(hipStream_t s, const SweepArgs& a, int64_t nblk);
 // ---- linalg (tgp_kernels_linalg.hip) ----
 void launch_scale_inputs(hipStream_t s, const double* X, const double* ls, double* Xs, int64_t N,
                          int64_t Npad, int d, int dp);
-void launch_assemble_K(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp,
-                       int kind, double variance, double noise, int64_t row0 = 0);
-void launch_assemble_K_batch(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
-                             const double* hyp, int64_t hyp_stride, int64_t a_stride, int B);
+hipError_t launch_assemble_K(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
+                             double variance, double noise, int64_t row0 = 0);
+hipError_t launch_assemble_K_batch(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
+                                   const double* hyp, int64_t hyp_stride, int64_t a_stride, int B);
 void launch_batch_prep(hipStream_t s, const double* X, const double* Y, const double* hyp, int64_t hyp_stride, int B,
                        double* Xs, double* err, int64_t N, int64_t Npad, int d, int dp);
 void launch_leaf(hipStream_t s, const double* A, double* L, double* W, int64_t ld, int64_t off,
@@ -220,7 +250,7 @@ inline F by_kind(F const (&family)[4], int kind) {
 }
 
 // ---- misc (tgp_kernels_misc.hip) ----
-void launch_predict_mean(hipStream_t s, const ModelDev& m, const double* Xq, int64_t M, double* mean);
+hipError_t launch_predict_mean(hipStream_t s, const ModelDev& m, const double* Xq, int64_t M, double* mean);
 void launch_argmax_final(hipStream_t s, const double* blk_val, const int64_t* blk_idx, int64_t n,
                          double* out_val, int64_t* out_idx);
 void launch_penalize(hipStream_t s, double* vals, const double* Xq, int64_t M, int d, int kind, int P,
@@ -266,18 +296,18 @@ void launch_predict_small_tail(hipStream_t s, const ModelDev& m, int64_t P, int6
                                double* part, double* mean_out, double* var_out);
 void launch_joint_pick(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, int q, const double* S, double* cov);
 void launch_joint_mix(hipStream_t s, const double* C1, const double* gcov, int64_t P, int64_t Ppad, int64_t Npad, int q, double* D);
-void launch_joint_vjp_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, int q, const double* B,
-                           const double* C1, const double* Z, double* part, const double* gmean, const double* gcov, double* grad);
+hipError_t launch_joint_vjp_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, int q,
+                                 const double* B, const double* C1, const double* Z, double* part, const double* gmean,
+                                 const double* gcov, double* grad);
 size_t grad_tail_scratch_doubles(int64_t Ppad, int dp);   // `part` of launch_grad_tail / launch_joint_vjp_tail
-void launch_grad_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad,
-                      const double* B, const double* C1, const double* Z, double* part, int acq, double param, double* val,
-                      double* grad, const double* samples = nullptr, int S = 0, double rep_w = 0.0,
-                      double accum = 0.0);
+hipError_t launch_grad_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, const double* B,
+                            const double* C1, const double* Z, double* part, int acq, double param, double* val, double* grad,
+                            const double* samples = nullptr, int S = 0, double rep_w = 0.0, double accum = 0.0);
 void launch_entropy_tail(hipStream_t s, const double* mean, const double* var, const double* var_twin, int64_t M,
                          int acq, double noise, const double* samples, int S, double weight, double* out);
 int64_t nlml_blocks(int64_t Npad);
-void launch_nlml(hipStream_t s, const ModelDev& m, const double* Kinv, const double* L, const double* err,
-                 double* partial, double* out);
+hipError_t launch_nlml(hipStream_t s, const ModelDev& m, const double* Kinv, const double* L, const double* err,
+                       double* partial, double* out);
 void launch_nlml_value(hipStream_t s, const ModelDev& m, const double* L, const double* err, double* out);
 void launch_nlml_value_batch(hipStream_t s, const ModelDev& m, const double* L, const double* z, double* out, int B,
                              int64_t l_stride, int64_t v_stride, int64_t o_stride);
@@ -292,11 +322,11 @@ struct TrajDev {
   const double* v;     // [Npad][B] canonical weights, zero padded
   int canonical;       // 1: decoupled trajectory (features + k(x, X) v); 0: RFF-only trajectory (features + mean)
 };
-void launch_rff_project(hipStream_t s, const TrajDev& t, const double* Xs_pts, int64_t npts,
-                        double* out /*[npts][B]*/);
-void launch_traj_eval(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, int per_traj,
-                      double* out, double* blk_val, int64_t* blk_idx, int64_t index_base);
-void launch_kernel_sums(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, double* out);
+hipError_t launch_rff_project(hipStream_t s, const TrajDev& t, const double* Xs_pts, int64_t npts,
+                              double* out /*[npts][B]*/);
+hipError_t launch_traj_eval(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, int per_traj,
+                            double* out, double* blk_val, int64_t* blk_idx, int64_t index_base);
+hipError_t launch_kernel_sums(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, double* out);
 void launch_lowrank_var(hipStream_t s, const double* var, const double* u, int64_t M, int m, double* var_out);
 void launch_rows_to_columns(hipStream_t s, const double* W, int64_t ld, int64_t row0, int m, int64_t n, double* out);
 void launch_prefix_differs(hipStream_t s, const double* a, const double* b, int64_t n, int* flag);
@@ -305,8 +335,8 @@ void launch_rff_features(hipStream_t s, const TrajDev& t, double scale, int64_t 
 void launch_sym_finish(hipStream_t s, double* A, int64_t n, int64_t np, double scale, double shift, int negate);
 void launch_theta_tail(hipStream_t s, const double* mean, int64_t ldm, const double* R, int64_t ldr, int F, int B,
                        double scale, double* theta, double* ws);
-void launch_traj_grad(hipStream_t s, const TrajDev& t, const double* Xq, int64_t nitems, double* val,
-                      double* grad);
+hipError_t launch_traj_grad(hipStream_t s, const TrajDev& t, const double* Xq, int64_t nitems, double* val,
+                            double* grad);
 // ---- `update` as one persistent launch (tgp_kernels_dag.hip) -----------------------------------------------------
 constexpr int DAG_MAT_A = 0, DAG_MAT_L = 1, DAG_MAT_W = 2;   // which matrix a tile offset refers to
 constexpr uint32_t DAG_NN = 1, DAG_BETA = 2, DAG_NEG = 4;     // B operand natural (else transposed); add Cin; negate

@@ -588,47 +588,49 @@ void launch_joint_mix(hipStream_t s, const double* C1, const double* gcov, int64
   hipLaunchKernelGGL(joint_mix_kernel, grid, dim3(256), 0, s, C1, gcov, P, Ppad, Npad, q, D);
 }
 
-static void launch_grad_partial(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, const double* B,
-                                const double* C1, const double* Z, double* part);
+static hipError_t launch_grad_partial(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad,
+                                      const double* B, const double* C1, const double* Z, double* part);
 
-void launch_joint_vjp_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, int q, const double* B,
-                           const double* C1, const double* Z, double* part, const double* gmean, const double* gcov,
-                           double* grad) {
-  launch_grad_partial(s, m, Xq, P, Ppad, B, C1, Z, part);
+hipError_t launch_joint_vjp_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, int q,
+                                 const double* B, const double* C1, const double* Z, double* part, const double* gmean,
+                                 const double* gcov, double* grad) {
+  const hipError_t e = launch_grad_partial(s, m, Xq, P, Ppad, B, C1, Z, part);
+  if (e != hipSuccess) return e;
   if (m.dp > MAX_D)
     hipLaunchKernelGGL(joint_vjp_finish_kernel<true>, dim3((unsigned)P), dim3(64), 0, s, m, Xq, P, Ppad, q, part, gmean, gcov, grad);
   else
     hipLaunchKernelGGL(joint_vjp_finish_kernel<false>, dim3((unsigned)P), dim3(64), 0, s, m, Xq, P, Ppad, q, part, gmean, gcov, grad);
+  return hipGetLastError();
 }
 
-static void launch_grad_partial(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, const double* B,
-                                const double* C1, const double* Z, double* part) {
+static hipError_t launch_grad_partial(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad,
+                                      const double* B, const double* C1, const double* Z, double* part) {
   const dim3 grid((unsigned)(Ppad / 16), (unsigned)GT_KS);
   if (m.dp > MAX_D) {   // the query points scaled once, behind the wide partials (grad_tail_scratch_doubles)
     double* const xsq = part + (size_t)GT_KS * (size_t)Ppad * gt_j(m.dp);
     launch_scale_inputs(s, Xq, m.ls, xsq, P, Ppad, m.d, m.dp);
     hipLaunchKernelGGL(grad_partial_wide_kernel, dim3((unsigned)(Ppad / 16), (unsigned)GT_KS, (unsigned)(m.dp / WIDE_CHUNK)),
                        dim3(GT_THREADS), 0, s, m, xsq, P, Ppad, B, C1, Z, part);
-    return;
+    return hipGetLastError();
   }
-  if (m.dp == 2) hipLaunchKernelGGL(grad_partial_kernel<2>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
-  else if (m.dp == 4) hipLaunchKernelGGL(grad_partial_kernel<4>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
-  else if (m.dp == 6) hipLaunchKernelGGL(grad_partial_kernel<6>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
-  else if (m.dp == 8) hipLaunchKernelGGL(grad_partial_kernel<8>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
-  else if (m.dp == 16) hipLaunchKernelGGL(grad_partial_kernel<16>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
-  else hipLaunchKernelGGL(grad_partial_kernel<32>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
+  return with_dp<MAX_D>(m.dp, [&](auto DP) {
+    hipLaunchKernelGGL(grad_partial_kernel<DP()>, grid, dim3(GT_THREADS), 0, s, m, Xq, P, Ppad, B, C1, Z, part);
+    return hipGetLastError();
+  });
 }
 
-void launch_grad_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad,
-                      const double* B, const double* C1, const double* Z, double* part, int acq, double param, double* val,
-                      double* grad, const double* samples, int S, double rep_w, double accum) {
-  launch_grad_partial(s, m, Xq, P, Ppad, B, C1, Z, part);
+hipError_t launch_grad_tail(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, const double* B,
+                            const double* C1, const double* Z, double* part, int acq, double param, double* val, double* grad,
+                            const double* samples, int S, double rep_w, double accum) {
+  const hipError_t e = launch_grad_partial(s, m, Xq, P, Ppad, B, C1, Z, part);
+  if (e != hipSuccess) return e;
   if (m.dp > MAX_D)
     hipLaunchKernelGGL(grad_finish_kernel<true>, dim3((unsigned)P), dim3(128), 0, s, m, P, Ppad, part, acq, param, samples, S, rep_w,
                        accum, val, grad);
   else
     hipLaunchKernelGGL(grad_finish_kernel<false>, dim3((unsigned)P), dim3(128), 0, s, m, P, Ppad, part, acq, param, samples, S,
                        rep_w, accum, val, grad);
+  return hipGetLastError();
 }
 
 }  // namespace tgp
@@ -899,25 +901,21 @@ void launch_nlml_value_batch(hipStream_t s, const ModelDev& m, const double* L, 
 
 int64_t nlml_blocks(int64_t Npad) { return (Npad / 64) * (Npad / 64); }
 
-void launch_nlml(hipStream_t s, const ModelDev& m, const double* Kinv, const double* L, const double* err,
-                 double* partial, double* out) {
+hipError_t launch_nlml(hipStream_t s, const ModelDev& m, const double* Kinv, const double* L, const double* err,
+                       double* partial, double* out) {
   dim3 grid((unsigned)(m.Npad / 64), (unsigned)(m.Npad / 64));
   if (m.dp > MAX_D) {
     hipLaunchKernelGGL(nlml_grad_wide_kernel, dim3(grid.x, grid.y, (unsigned)(m.dp / WIDE_CHUNK)), dim3(256), 0, s, m, Kinv,
                        partial);
     hipLaunchKernelGGL(nlml_final_wide_kernel, dim3(1), dim3(m.N > 1024 ? 1024 : 256), 0, s, m, L, err, partial,
                        nlml_blocks(m.Npad), out, (int64_t)0, (int64_t)0, (int64_t)0);
-    return;
+    return hipGetLastError();
   }
-  switch (m.dp) {
-    case 2: hipLaunchKernelGGL(nlml_grad_kernel<2>, grid, dim3(256), 0, s, m, Kinv, partial); break;
-    case 4: hipLaunchKernelGGL(nlml_grad_kernel<4>, grid, dim3(256), 0, s, m, Kinv, partial); break;
-    case 6: hipLaunchKernelGGL(nlml_grad_kernel<6>, grid, dim3(256), 0, s, m, Kinv, partial); break;
-    case 8: hipLaunchKernelGGL(nlml_grad_kernel<8>, grid, dim3(256), 0, s, m, Kinv, partial); break;
-    case 16: hipLaunchKernelGGL(nlml_grad_kernel<16>, grid, dim3(256), 0, s, m, Kinv, partial); break;
-    default: hipLaunchKernelGGL(nlml_grad_kernel<32>, grid, dim3(256), 0, s, m, Kinv, partial); break;
-  }
-  hipLaunchKernelGGL(nlml_final_kernel, dim3(1), dim3(m.N > 1024 ? 1024 : 256), 0, s, m, L, err, partial, nlml_blocks(m.Npad), out);
+  return with_dp<MAX_D>(m.dp, [&](auto DP) {
+    hipLaunchKernelGGL(nlml_grad_kernel<DP()>, grid, dim3(256), 0, s, m, Kinv, partial);
+    hipLaunchKernelGGL(nlml_final_kernel, dim3(1), dim3(m.N > 1024 ? 1024 : 256), 0, s, m, L, err, partial, nlml_blocks(m.Npad), out);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace tgp

@@ -395,15 +395,10 @@ __global__ __launch_bounds__(1024, 4) void joint_kernel(const SweepArgs a) {
 template <int KIND>
 hipError_t launch_joint_dp(hipStream_t s, const SweepArgs& a, int64_t grid) {
   dim3 g((unsigned)grid), b(1024);
-  switch (a.m.dp) {
-    case 2: hipLaunchKernelGGL((joint_kernel<KIND, 2>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((joint_kernel<KIND, 4>), g, b, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((joint_kernel<KIND, 6>), g, b, 0, s, a); break;
-    case 8: hipLaunchKernelGGL((joint_kernel<KIND, 8>), g, b, 0, s, a); break;
-    case 16: hipLaunchKernelGGL((joint_kernel<KIND, 16>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dp<16>(a.m.dp, [&](auto DP) {
+    hipLaunchKernelGGL((joint_kernel<KIND, DP()>), g, b, 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace

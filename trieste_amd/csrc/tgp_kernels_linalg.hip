@@ -137,46 +137,32 @@ __global__ __launch_bounds__(256) void assemble_K_kernel(const double* __restric
   }
 }
 
-template <int KIND>
-static void launch_assemble_K_dp(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp,
-                                 double variance, double noise, int64_t row0, const double* hyp, int64_t hyp_stride,
-                                 int64_t a_stride, int B) {
+static hipError_t launch_assemble_K_any(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
+                                        double variance, double noise, int64_t row0, const double* hyp, int64_t hyp_stride,
+                                        int64_t a_stride, int B) {
   // A is addressed with GLOBAL row indices: for row0 > 0 the caller passes (scratch - row0 * Npad)
   dim3 g((unsigned)(Npad / 64), (unsigned)((Npad - row0) / 64), (unsigned)B), b(256);
-#define TGP_ASM_K(DPV) \
-  hipLaunchKernelGGL((assemble_K_kernel<KIND, DPV>), g, b, 0, s, Xs, A, N, Npad, variance, noise, row0, hyp, hyp_stride, a_stride, dp)
-  switch (dp) {
-    case 2: TGP_ASM_K(2); break;
-    case 4: TGP_ASM_K(4); break;
-    case 6: TGP_ASM_K(6); break;
-    case 8: TGP_ASM_K(8); break;
-    case 16: TGP_ASM_K(16); break;
-    case 32: TGP_ASM_K(32); break;
-    default: TGP_ASM_K(DP_WIDE); break;
-  }
-#undef TGP_ASM_K
+  return with_kind(kind, [&](auto kind_c) {
+    constexpr int KIND = kind_c();
+    auto launch = [&](auto DP) {
+      hipLaunchKernelGGL((assemble_K_kernel<KIND, DP()>), g, b, 0, s, Xs, A, N, Npad, variance, noise, row0, hyp, hyp_stride,
+                         a_stride, dp);
+      return hipGetLastError();
+    };
+    if (dp <= MAX_D) return with_dp<MAX_D>(dp, launch);
+    return dp % WIDE_CHUNK == 0 ? launch(std::integral_constant<int, DP_WIDE>{}) : hipErrorInvalidValue;
+  });
 }
 
-static void launch_assemble_K_any(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
-                                  double variance, double noise, int64_t row0, const double* hyp, int64_t hyp_stride,
-                                  int64_t a_stride, int B) {
-  switch (kind) {
-    case KIND_RBF: launch_assemble_K_dp<KIND_RBF>(s, Xs, A, N, Npad, dp, variance, noise, row0, hyp, hyp_stride, a_stride, B); break;
-    case KIND_M12: launch_assemble_K_dp<KIND_M12>(s, Xs, A, N, Npad, dp, variance, noise, row0, hyp, hyp_stride, a_stride, B); break;
-    case KIND_M32: launch_assemble_K_dp<KIND_M32>(s, Xs, A, N, Npad, dp, variance, noise, row0, hyp, hyp_stride, a_stride, B); break;
-    default: launch_assemble_K_dp<KIND_M52>(s, Xs, A, N, Npad, dp, variance, noise, row0, hyp, hyp_stride, a_stride, B); break;
-  }
-}
-
-void launch_assemble_K(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp,
-                       int kind, double variance, double noise, int64_t row0) {
-  launch_assemble_K_any(s, Xs, A, N, Npad, dp, kind, variance, noise, row0, nullptr, 0, 0, 1);
+hipError_t launch_assemble_K(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
+                             double variance, double noise, int64_t row0) {
+  return launch_assemble_K_any(s, Xs, A, N, Npad, dp, kind, variance, noise, row0, nullptr, 0, 0, 1);
 }
 // B members in one launch: member b's inputs at Xs + b Npad dp, its matrix at A + b a_stride, its (variance, noise) at
 // hyp [b hyp_stride + 32 / 33]
-void launch_assemble_K_batch(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
-                             const double* hyp, int64_t hyp_stride, int64_t a_stride, int B) {
-  launch_assemble_K_any(s, Xs, A, N, Npad, dp, kind, 0.0, 0.0, 0, hyp, hyp_stride, a_stride, B);
+hipError_t launch_assemble_K_batch(hipStream_t s, const double* Xs, double* A, int64_t N, int64_t Npad, int dp, int kind,
+                                   const double* hyp, int64_t hyp_stride, int64_t a_stride, int B) {
+  return launch_assemble_K_any(s, Xs, A, N, Npad, dp, kind, 0.0, 0.0, 0, hyp, hyp_stride, a_stride, B);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -108,35 +108,23 @@ __global__ __launch_bounds__(256) void predict_mean_wide_kernel(ModelDev m, cons
   }
 }
 
-void launch_predict_mean(hipStream_t s, const ModelDev& m, const double* Xq, int64_t M, double* mean) {
+hipError_t launch_predict_mean(hipStream_t s, const ModelDev& m, const double* Xq, int64_t M, double* mean) {
+  const bool wave = M <= 32768;   // a wave per query, else a thread per query
+  dim3 g((unsigned)(wave ? (M + 3) / 4 : (M + 255) / 256)), b(256);
   if (m.dp > MAX_D) {
-    if (M <= 32768)
-      hipLaunchKernelGGL(predict_mean_wide_kernel<true>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, m, Xq, M, mean);
-    else
-      hipLaunchKernelGGL(predict_mean_wide_kernel<false>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, m, Xq, M, mean);
-    return;
+    if (wave) hipLaunchKernelGGL(predict_mean_wide_kernel<true>, g, b, 0, s, m, Xq, M, mean);
+    else hipLaunchKernelGGL(predict_mean_wide_kernel<false>, g, b, 0, s, m, Xq, M, mean);
+    return hipGetLastError();
   }
-  if (M <= 32768) {
-    dim3 g((unsigned)((M + 3) / 4)), b(256);
-    switch (m.dp) {
-      case 2: hipLaunchKernelGGL(predict_mean_wave_kernel<2>, g, b, 0, s, m, Xq, M, mean); break;
-      case 4: hipLaunchKernelGGL(predict_mean_wave_kernel<4>, g, b, 0, s, m, Xq, M, mean); break;
-      case 6: hipLaunchKernelGGL(predict_mean_wave_kernel<6>, g, b, 0, s, m, Xq, M, mean); break;
-      case 8: hipLaunchKernelGGL(predict_mean_wave_kernel<8>, g, b, 0, s, m, Xq, M, mean); break;
-      case 16: hipLaunchKernelGGL(predict_mean_wave_kernel<16>, g, b, 0, s, m, Xq, M, mean); break;
-      default: hipLaunchKernelGGL(predict_mean_wave_kernel<32>, g, b, 0, s, m, Xq, M, mean); break;
-    }
-    return;
-  }
-  dim3 g((unsigned)((M + 255) / 256)), b(256);
-  switch (m.dp) {
-    case 2: hipLaunchKernelGGL(predict_mean_kernel<2>, g, b, 0, s, m, Xq, M, mean); break;
-    case 4: hipLaunchKernelGGL(predict_mean_kernel<4>, g, b, 0, s, m, Xq, M, mean); break;
-    case 6: hipLaunchKernelGGL(predict_mean_kernel<6>, g, b, 0, s, m, Xq, M, mean); break;
-    case 8: hipLaunchKernelGGL(predict_mean_kernel<8>, g, b, 0, s, m, Xq, M, mean); break;
-    case 16: hipLaunchKernelGGL(predict_mean_kernel<16>, g, b, 0, s, m, Xq, M, mean); break;
-    default: hipLaunchKernelGGL(predict_mean_kernel<32>, g, b, 0, s, m, Xq, M, mean); break;
-  }
+  if (wave)
+    return with_dp<MAX_D>(m.dp, [&](auto DP) {
+      hipLaunchKernelGGL(predict_mean_wave_kernel<DP()>, g, b, 0, s, m, Xq, M, mean);
+      return hipGetLastError();
+    });
+  return with_dp<MAX_D>(m.dp, [&](auto DP) {
+    hipLaunchKernelGGL(predict_mean_kernel<DP()>, g, b, 0, s, m, Xq, M, mean);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -436,18 +436,13 @@ __global__ __launch_bounds__(1024, 4) void sweep_kernel(const SweepArgs a) {
 template <int KIND, bool JOINT, bool SPLIT>
 hipError_t launch_sweep_dp(hipStream_t s, const SweepArgs& a, int64_t grid) {
   dim3 g((unsigned)grid), b(1024);
-  switch (a.m.dp) {
-    case 2: hipLaunchKernelGGL((sweep_kernel<KIND, 2, JOINT, SPLIT>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((sweep_kernel<KIND, 4, JOINT, SPLIT>), g, b, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((sweep_kernel<KIND, 6, JOINT, SPLIT>), g, b, 0, s, a); break;
-    case 8: hipLaunchKernelGGL((sweep_kernel<KIND, 8, JOINT, SPLIT>), g, b, 0, s, a); break;
-    case 16: hipLaunchKernelGGL((sweep_kernel<KIND, 16, JOINT, SPLIT>), g, b, 0, s, a); break;
-    case 32: hipLaunchKernelGGL((sweep_kernel<KIND, 32, JOINT, SPLIT>), g, b, 0, s, a); break;
-    default:
-      if (a.m.dp <= MAX_D || a.m.dp % WIDE_CHUNK != 0 || !a.xqw) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((sweep_kernel<KIND, DP_WIDE, JOINT, SPLIT>), g, b, 0, s, a);
-      break;
-  }
+  if (a.m.dp <= MAX_D)
+    return with_dp<MAX_D>(a.m.dp, [&](auto DP) {
+      hipLaunchKernelGGL((sweep_kernel<KIND, DP(), JOINT, SPLIT>), g, b, 0, s, a);
+      return hipGetLastError();
+    });
+  if (a.m.dp % WIDE_CHUNK != 0 || !a.xqw) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((sweep_kernel<KIND, DP_WIDE, JOINT, SPLIT>), g, b, 0, s, a);
   return hipGetLastError();
 }
 

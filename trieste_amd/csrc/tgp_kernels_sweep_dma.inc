@@ -717,15 +717,10 @@ void launch_prune_mean(hipStream_t s, const SweepArgs& a, int64_t wg, int waves)
 template <int KIND, bool PRUNE>
 hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) {
   dim3 g((unsigned)grid), b(1024);
-  switch (a.m.dp) {
-    case 2: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 2, PRUNE>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 4, PRUNE>), g, b, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 6, PRUNE>), g, b, 0, s, a); break;
-    case 8: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 8, PRUNE>), g, b, 0, s, a); break;
-    case 16: hipLaunchKernelGGL((sweep_dma_kernel<KIND, 16, PRUNE>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dp<16>(a.m.dp, [&](auto DP) {
+    hipLaunchKernelGGL((sweep_dma_kernel<KIND, DP(), PRUNE>), g, b, 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
@@ -740,16 +735,13 @@ hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) 
 // stream order, no host synchronisation; what depends on the number of survivors is decided on the device.
 hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid, const PruneLaunch& pl) {
   if (a.m.Npad / DBM <= 1) return launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
-  switch (a.m.dp) {
-    case 2: launch_prune_mean<TGP_SWEEP_KIND, 2>(s, a, grid, pl.mean_waves); break;
-    case 4: launch_prune_mean<TGP_SWEEP_KIND, 4>(s, a, grid, pl.mean_waves); break;
-    case 6: launch_prune_mean<TGP_SWEEP_KIND, 6>(s, a, grid, pl.mean_waves); break;
-    case 8: launch_prune_mean<TGP_SWEEP_KIND, 8>(s, a, grid, pl.mean_waves); break;
-    case 16: launch_prune_mean<TGP_SWEEP_KIND, 16>(s, a, grid, pl.mean_waves); break;
-    default: return hipErrorInvalidValue;
-  }
+  hipError_t e = with_dp<16>(a.m.dp, [&](auto DP) {
+    launch_prune_mean<TGP_SWEEP_KIND, DP()>(s, a, grid, pl.mean_waves);
+    return hipSuccess;
+  });
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(prune_list_kernel, dim3(1), dim3(1024), 0, s, a, pl, (int)grid);
-  hipError_t e = launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
+  e = launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
   if (e != hipSuccess) return e;
   if (pl.max_survivors > 0) hipLaunchKernelGGL(prune_fold_kernel, dim3((unsigned)pl.max_survivors), dim3(1024), 0, s, a);
   return hipGetLastError();

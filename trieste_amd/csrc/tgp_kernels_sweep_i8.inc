@@ -714,26 +714,14 @@ hipError_t launch_sweep_i8_dp(hipStream_t s, const SweepArgs& a, int64_t grid) {
   const size_t shmem = (size_t)i8_lds_bytes(NS, a.m.dp, tiles);
   if (shmem > 160 * 1024) return hipErrorInvalidValue;  // NS = 5 with dp = 32
   if (tiles && !a.i8_xsa) return hipErrorInvalidValue;
-#define TGP_I8_CASE(DPV)                                                                                     \
-  case DPV: {                                                                                                \
-    /* > 64 KiB of dynamic LDS is opt-in, per function and per device: set on every launch (a few us) */      \
-    hipError_t e = hipFuncSetAttribute((const void*)sweep_i8_kernel<KIND, DPV, NS>,                          \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);              \
-    if (e != hipSuccess) return e;                                                                           \
-    hipLaunchKernelGGL((sweep_i8_kernel<KIND, DPV, NS>), g, b, shmem, s, a);                                 \
-    break;                                                                                                   \
-  }
-  switch (a.m.dp) {
-    TGP_I8_CASE(2)
-    TGP_I8_CASE(4)
-    TGP_I8_CASE(6)
-    TGP_I8_CASE(8)
-    TGP_I8_CASE(16)
-    TGP_I8_CASE(32)
-    default: return hipErrorInvalidValue;
-  }
-#undef TGP_I8_CASE
-  return hipGetLastError();
+  return with_dp<MAX_D>(a.m.dp, [&](auto DP) {
+    // > 64 KiB of dynamic LDS is opt-in, per function and per device: set on every launch (a few us)
+    hipError_t e = hipFuncSetAttribute((const void*)sweep_i8_kernel<KIND, DP(), NS>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((sweep_i8_kernel<KIND, DP(), NS>), g, b, shmem, s, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace

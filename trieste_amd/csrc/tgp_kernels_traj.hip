@@ -186,27 +186,16 @@ static void launch_traj_bp(hipStream_t s, const TrajDev& t, const double* Xq, in
 #undef TGP_TRAJ_LAUNCH
 }
 
-template <int KIND>
-static void launch_traj_dp(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, int per_traj,
-                           int rff_only, double* out, double* bv, int64_t* bi, int64_t base) {
-  switch (t.m.dp) {
-    case 2: launch_traj_bp<KIND, 2>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    case 4: launch_traj_bp<KIND, 4>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    case 6: launch_traj_bp<KIND, 6>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    case 8: launch_traj_bp<KIND, 8>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    case 16: launch_traj_bp<KIND, 16>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    default: launch_traj_bp<KIND, 32>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-  }
-}
-
-static void launch_traj_any(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, int per_traj,
-                            int rff_only, double* out, double* bv, int64_t* bi, int64_t base) {
-  switch (t.m.kind) {
-    case KIND_RBF: launch_traj_dp<KIND_RBF>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    case KIND_M12: launch_traj_dp<KIND_M12>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    case KIND_M32: launch_traj_dp<KIND_M32>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-    default: launch_traj_dp<KIND_M52>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base); break;
-  }
+// (there is no wide form of the trajectory kernels: dp > MAX_D is refused here like any dp outside the list)
+static hipError_t launch_traj_any(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, int per_traj,
+                                  int rff_only, double* out, double* bv, int64_t* bi, int64_t base) {
+  return with_kind(t.m.kind, [&](auto kind_c) {
+    constexpr int KIND = kind_c();
+    return with_dp<MAX_D>(t.m.dp, [&](auto DP) {
+      launch_traj_bp<KIND, DP()>(s, t, Xq, M, per_traj, rff_only, out, bv, bi, base);
+      return hipGetLastError();
+    });
+  });
 }
 
 int64_t traj_grid(int64_t M) { return (M + 255) / 256; }
@@ -214,13 +203,13 @@ int64_t traj_grid(int64_t M) { return (M + 255) / 256; }
 // out[M][B] = sum_k k(x, X_k) v[k][b] for B <= 16 weight vectors over the model's training inputs (t.F must be 0):
 // the m = rank-of-the-update dot products GIBBON's conditioned variance needs per candidate (prepare_repulsion takes the
 // low-rank path for m <= 16 only: the masked 16-column form writes no column beyond that).
-void launch_kernel_sums(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, double* out) {
-  launch_traj_any(s, t, Xq, M, 0, 3, out, nullptr, nullptr, 0);
+hipError_t launch_kernel_sums(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, double* out) {
+  return launch_traj_any(s, t, Xq, M, 0, 3, out, nullptr, nullptr, 0);
 }
 
-void launch_traj_eval(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, int per_traj,
-                      double* out, double* blk_val, int64_t* blk_idx, int64_t index_base) {
-  launch_traj_any(s, t, Xq, M, per_traj, t.canonical ? 0 : 2, out, blk_val, blk_idx, index_base);
+hipError_t launch_traj_eval(hipStream_t s, const TrajDev& t, const double* Xq, int64_t M, int per_traj,
+                            double* out, double* blk_val, int64_t* blk_idx, int64_t index_base) {
+  return launch_traj_any(s, t, Xq, M, per_traj, t.canonical ? 0 : 2, out, blk_val, blk_idx, index_base);
 }
 
 // Value and gradient of trajectory b at its own point x[p][b][:] -- the pair the L-BFGS-B
@@ -283,17 +272,13 @@ __global__ __launch_bounds__(256) void traj_grad_kernel(TrajDev t, const double*
   }
 }
 
-void launch_traj_grad(hipStream_t s, const TrajDev& t, const double* Xq, int64_t nitems, double* val,
-                      double* grad) {
+hipError_t launch_traj_grad(hipStream_t s, const TrajDev& t, const double* Xq, int64_t nitems, double* val,
+                            double* grad) {
   dim3 g((unsigned)nitems), b(256);
-  switch (t.m.dp) {
-    case 2: hipLaunchKernelGGL(traj_grad_kernel<2>, g, b, 0, s, t, Xq, nitems, val, grad); break;
-    case 4: hipLaunchKernelGGL(traj_grad_kernel<4>, g, b, 0, s, t, Xq, nitems, val, grad); break;
-    case 6: hipLaunchKernelGGL(traj_grad_kernel<6>, g, b, 0, s, t, Xq, nitems, val, grad); break;
-    case 8: hipLaunchKernelGGL(traj_grad_kernel<8>, g, b, 0, s, t, Xq, nitems, val, grad); break;
-    case 16: hipLaunchKernelGGL(traj_grad_kernel<16>, g, b, 0, s, t, Xq, nitems, val, grad); break;
-    default: hipLaunchKernelGGL(traj_grad_kernel<32>, g, b, 0, s, t, Xq, nitems, val, grad); break;
-  }
+  return with_dp<MAX_D>(t.m.dp, [&](auto DP) {
+    hipLaunchKernelGGL(traj_grad_kernel<DP()>, g, b, 0, s, t, Xq, nitems, val, grad);
+    return hipGetLastError();
+  });
 }
 
 // Phi[i][f] = sqrt(2 variance / F) cos(Xs_i . W_f + b_f) for the N training rows, [Npad][Fp] zero padded
@@ -318,8 +303,8 @@ void launch_rff_features(hipStream_t s, const TrajDev& t, double scale, int64_t 
 
 // Phi_Z w at a set of RAW points (the training inputs): out [npts][B] = sum_f phi_f(x) ws[f][b]
 // (sampler.py:726 `phi_Z @ prior_weights`).  The shared-input form: t.B <= 16 (tgp_traj_create hands wider sets over in groups).
-void launch_rff_project(hipStream_t s, const TrajDev& t, const double* X_raw, int64_t npts, double* out) {
-  launch_traj_any(s, t, X_raw, npts, 0, 1, out, nullptr, nullptr, 0);
+hipError_t launch_rff_project(hipStream_t s, const TrajDev& t, const double* X_raw, int64_t npts, double* out) {
+  return launch_traj_any(s, t, X_raw, npts, 0, 1, out, nullptr, nullptr, 0);
 }
 
 }  // namespace tgp
