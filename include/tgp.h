@@ -523,6 +523,14 @@ int tgp_get_prune_counters(tgp_handle h, int64_t* blocks, int64_t* given_up, int
  * variance cannot win), before any slab store, DMA or row block.  0 when the most recent arg-max did not run the pruned
  * kernel, at Npad = 256 (one row block: nothing is given up) and under tgp_set_variant bit 12.  Synchronises the stream. */
 int tgp_get_prune_screened(tgp_handle h, int64_t* screened);
+/* Of the blocks given up by the mean screen, those a float32 pre-screen dismissed first (phase 0): their
+ * float64 mean pass did not run.  Never more than tgp_get_prune_screened; 0 under tgp_set_variant bits 12 and 14, at
+ * Npad = 256 and when the most recent arg-max did not run the pruned kernel.  Synchronises the handle's stream. */
+int tgp_get_prune_prescreened(tgp_handle h, int64_t* prescreened);
+/* The pre-screen's own quantities for M candidates Xq [M][d] (d <= 16): `mean32`, the posterior mean as the device forms it
+ * in float32 kernel arithmetic, and `E`, the a-priori bound it holds for |mean32 - mean| per candidate.  A test and
+ * measurement aid; `where` as in tgp_predict. */
+int tgp_prescreen_means(tgp_handle h, const double* Xq, int64_t M, double* mean32, double* E, int where);
 /* Models of more than one row block (Npad > 256) run the pruned arg-max in three phases: the mean pass of every block, the
  * blocks that survive the mean screen, a fold of what the split survivors left.  When at most `max_survivors`
  * blocks survive, each is cut into up to `max_groups` contiguous ranges of row blocks and the ranges are spread over the
@@ -616,8 +624,9 @@ int tgp_get_auto_strata(tgp_handle h, int64_t* checked2, int64_t* violations2, d
  * set -- and, for tgp_predict, no arithmetic other than float64; joint mode is float64 on every path), bit 11 = the fused EI
  * arg-max sweeps every candidate block to the end instead of giving up blocks that cannot win (same winner, bit for bit), bit 12 =
  * the pruned EI arg-max without the seed and the mean screen (blocks are given up at row-block boundaries only), bit 13 = its
- * workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter (bits 12, 13: A/B runs and tests; the
- * same winner, bit for bit, under every combination).  Bits 0-3, 7, 8: every
+ * workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter, bit 14 =
+ * its exact mean pass over every block, without the float32 pre-screen in front (bits 12 - 14: A/B runs and tests; the
+ * same winner and the same counters, bit for bit, under every combination).  Bits 0-3, 7, 8: every
  * setting computes the same arithmetic on every candidate / matrix entry, bit for bit; bits 4 - 6, 9: the same values up to the
  * rounding of another summation order (bit 10 as well). */
 int tgp_set_variant(tgp_handle h, int variant);

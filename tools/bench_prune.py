@@ -3,7 +3,7 @@
 Two thresholds with the engine calls of bench.py's step: the model's eta (blocks are given up: the gain, with the
 counters of one step) and eta = -1e6 (every EI is 0, nothing can be given up: what the pruned kernel's generate-first
 phase and its checkpoints cost when they buy nothing).  --variant 2048 runs the unpruned kernel for the comparison, 4096 the pruned one
-without the seed and the mean screen, 8192 with blocks dealt statically (and 4096 | 8192 both); on a
+without the seed and the mean screen, 8192 with blocks dealt statically (and 4096 | 8192 both), 16384 without the float32 pre-screen; on a
 tree without the pruned kernel the counters are left out (TGP_TREE=<checkout> imports the package of another checkout,
 e.g. the parent commit's, for the same-box comparison).  Each line carries the survivors of the list screen and the split
 work items (0: the survivors ran whole); --max-survivors 0 switches the split regime off, --max-groups caps the ranges per block.
@@ -57,6 +57,8 @@ for label, eta in (("eta", eng.eta()), ("eta=-1e6", -1e6)):
         out["blocks, given up, row blocks skipped"] = E.prune_counters(eng)
     if hasattr(E, "prune_screened"):
         out["screened"] = E.prune_screened(eng)
+    if hasattr(E, "prune_prescreened"):
+        out["prescreened"] = E.prune_prescreened(eng)
     if hasattr(E, "prune_split"):
         out["survivors, items"] = E.prune_split(eng)
     print(json.dumps(out), flush=True)

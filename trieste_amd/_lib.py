@@ -106,6 +106,8 @@ SIGNATURES = {
     "tgp_last_kernel_ms": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),
     "tgp_get_prune_counters": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tgp_get_prune_screened": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "tgp_get_prune_prescreened": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "tgp_prescreen_means": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int]),
     "tgp_set_prune_split": (C.c_int, [_vp, C.c_int, C.c_int]),
     "tgp_get_prune_split": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tgp_set_variant": (C.c_int, [_vp, C.c_int]),

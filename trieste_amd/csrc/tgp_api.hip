@@ -176,7 +176,8 @@ void apply_penalization(tgp_handle h, double* dvals, const double* dXq, int64_t 
 constexpr int VARIANT_NO_SPLIT = 1, VARIANT_FORCE_SPLIT = 2, VARIANT_JOINT_V1 = 4, VARIANT_REG_STAGING = 8, VARIANT_NO_DAG = 16,
               VARIANT_DAG_SMALL = 32, VARIANT_NO_REPAIR_PRODUCT = 64, VARIANT_STATIC_BLOCKS = 128, VARIANT_DAG_WHOLE_TILES = 256,
               VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024, VARIANT_NO_PRUNE = 2048,
-              VARIANT_PRUNE_NO_SCREEN = 4096, VARIANT_PRUNE_STATIC_BLOCKS = 8192;
+              VARIANT_PRUNE_NO_SCREEN = 4096, VARIANT_PRUNE_STATIC_BLOCKS = 8192, VARIANT_PRUNE_NO_PRESCREEN = 16384;
+//   VARIANT_PRUNE_NO_PRESCREEN (16384): its mean pass over every block, without the float32 pre-screen in front (phase 0)
 //   VARIANT_PRUNE_NO_SCREEN (4096): the pruned EI arg-max without the seed and the mean screen (blocks are given up at checkpoints only)
 //   VARIANT_PRUNE_STATIC_BLOCKS (8192): its workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter
 //   VARIANT_SWEEP_SMALL_PREDICT (1024): tgp_predict at <= 2048 points through a sweep launch (rounds 1 - 5) instead of the skinny product
@@ -617,7 +618,7 @@ hipError_t launch_sweep_timed(tgp_handle h, SweepArgs a, bool joint) {
     // at a row-block boundary (PRUNE instantiation; the same winner bit for bit)
     const bool prune = a.acq_kind == TGP_ACQ_EI && a.blk_val && !a.acq_out && !a.mean_out && !a.var_out &&
                        !(h->variant & VARIANT_NO_PRUNE);
-    PruneLaunch pl{0, 0, 8};
+    PruneLaunch pl{0, 0, 8, nullptr, nullptr, nullptr, nullptr};
     if (prune) {
       // more than one row block: three phases; the split cap on S and with it the dump area follow from the bound on the dump
       // (no more than PRUNE_DUMP_MAX_BYTES, no more than the K* slabs: at most one survivor per workgroup), DESIGN.md 4.1
@@ -630,6 +631,12 @@ hipError_t launch_sweep_timed(tgp_handle h, SweepArgs a, bool joint) {
         static const bool mean4 = getenv("TGP_PRUNE_MEAN_WAVES4") != nullptr;  // A/B aid: phase 1 at four waves per SIMD
         pl.mean_waves = mean4 ? 4 : 8;
         words = PruneView::words(grid, pl.max_survivors, nb);
+        // phase 0 reads what `update` left for THIS handle's model (a sweep over another handle's model does without)
+        if (!(h->variant & (VARIANT_PRUNE_NO_SCREEN | VARIANT_PRUNE_NO_PRESCREEN)) && a.m.alpha == h->d_alpha.as<double>() &&
+            a.m.xc == h->d_xc.as<double>() && a.m.Npad == h->Npad) {
+          pl.xc32 = h->d_xc32.as<float>();
+          pl.pre = h->d_pre.as<double>();
+        }
       }
       ea = h->s_prune.reserve(words * sizeof(unsigned long long));
       if (ea != hipSuccess) return ea;
@@ -1134,7 +1141,7 @@ int tgp_destroy(tgp_handle h) {
   } else if (h->stream == nullptr) {
     (void)hipStreamSynchronize(nullptr);
   }
-  for (DevBuf* b : {&h->d_xc, &h->d_xn, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
+  for (DevBuf* b : {&h->d_xc, &h->d_xn, &h->d_xc32, &h->d_pre, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
                     &h->d_err, &h->d_tmp1, &h->d_tmp2, &h->d_info, &h->d_pen, &h->d_ent, &h->d_ehvi, &h->s_ehvi, &h->d_repv, &h->d_wq, &h->d_rs, &h->d_xsa, &h->s_ent, &h->s_in, &h->s_in2, &h->s_out1,
                     &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_xqw, &h->s_rep, &h->s_prune,
                     &h->s_rep_stats, &h->d_dag_flags, &h->d_dag_trace})
@@ -1330,6 +1337,8 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
   HIPCHK(h, h->d_Xs.reserve((size_t)Npad * dp * sizeof(double)));
   HIPCHK(h, h->d_xc.reserve((size_t)Npad * dp * sizeof(double)));
   HIPCHK(h, h->d_xn.reserve((size_t)Npad * sizeof(double)));
+  HIPCHK(h, h->d_xc32.reserve((size_t)Npad * dp * sizeof(float)));
+  HIPCHK(h, h->d_pre.reserve(PRE_WORDS * sizeof(double)));
   if (keep_rows == 0) {
     HIPCHK(h, h->d_A.reserve(nn));
     HIPCHK(h, h->d_L.reserve(nn));
@@ -1417,6 +1426,8 @@ static int factorise(tgp_handle h, int64_t N, int64_t keep_rows, double* trial_v
     launch_trmv(s, W, Npad, Npad, h->d_err.as<double>(), h->d_tmp2.as<double>(), true);
     launch_trmv(s, A, Npad, Npad, h->d_tmp2.as<double>(), h->d_alpha.as<double>(), false);
     // the padding rows of W carry the identity: alpha/tmp there are err_pad = 0 -> stay 0.
+    // what the float32 pre-screen of the pruned arg-max reads: the float32 centred rows, |alpha|_1 and the rows' extent
+    if (dp <= 16) launch_prescreen_prep(s, model_dev(h), h->d_xc32.as<float>(), h->d_pre.as<double>());
     if (trial_value) {  // (below the persistent kernel's sizes a trial is a full update)
       HIPCHK(h, h->s_small.reserve(64 + (std::max(h->dp, MAX_D) + 8) * sizeof(double)));
       trial_out = h->s_small.as<double>() + 8;
@@ -1816,6 +1827,8 @@ int tgp_clone_from(tgp_handle dst, tgp_handle src) {
     HIPCHK(dst, copy(dst->d_Xs, src->d_Xs, Npad * src->dp * sizeof(double)));
     HIPCHK(dst, copy(dst->d_xc, src->d_xc, Npad * src->dp * sizeof(double)));
     HIPCHK(dst, copy(dst->d_xn, src->d_xn, Npad * sizeof(double)));
+    HIPCHK(dst, copy(dst->d_xc32, src->d_xc32, Npad * src->dp * sizeof(float)));
+    HIPCHK(dst, copy(dst->d_pre, src->d_pre, PRE_WORDS * sizeof(double)));
     HIPCHK(dst, copy(dst->d_A, src->d_A, nn));
     HIPCHK(dst, copy(dst->d_L, src->d_L, nn));
     HIPCHK(dst, copy(dst->d_W, src->d_W, nn));
@@ -3088,6 +3101,45 @@ int tgp_get_prune_screened(tgp_handle h, int64_t* screened) {
   if (int rc = read_prune_words(h, w)) return rc;
   if (screened) *screened = (int64_t)w[PRUNE_W_SCREENED];
   return TGP_OK;
+}
+
+int tgp_get_prune_prescreened(tgp_handle h, int64_t* prescreened) {
+  if (!h) return TGP_ERR_ARG;
+  unsigned long long w[PRUNE_W_IB];
+  if (int rc = read_prune_words(h, w)) return rc;
+  if (prescreened) *prescreened = (int64_t)w[PRUNE_W_PRESCREENED];
+  return TGP_OK;
+}
+
+// phase 0 of the pruned arg-max alone, over the given candidates: what the device takes for mean32 and for its bound E
+int tgp_prescreen_means(tgp_handle h, const double* Xq, int64_t M, double* mean32, double* E, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (!h->have_data) return fail(h, TGP_ERR_STATE, "model has no data: call tgp_set_data first");
+  if (h->dp > 16) return fail(h, TGP_ERR_SHAPE, "the float32 pre-screen covers d <= 16 (d = %d)", h->d);
+  if (M < 0 || (M > 0 && (!Xq || !mean32 || !E))) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (M == 0) return TGP_OK;
+  if (int rc = set_device(h)) return rc;
+  const double* dXq;
+  double *dm, *de;
+  if (int rc = stage_in(h, h->s_in, Xq, (size_t)M * h->d, where, &dXq)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out1, mean32, M, where, &dm)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out2, E, M, where, &de)) return rc;
+  SweepArgs a{};
+  a.m = model_dev(h);
+  a.Xq = dXq;
+  a.M = M;
+  a.acq_kind = TGP_ACQ_EI;
+  a.acq_param = 0.0;
+  const int64_t nblk = (M + SW_BN - 1) / SW_BN;
+  h->prune_blocks = 0;   // the header words below are not an arg-max's
+  HIPCHK(h, h->s_prune.reserve(PruneView::words(nblk, 0, 1) * sizeof(unsigned long long)));
+  a.prune = h->s_prune.as<unsigned long long>();
+  HIPCHK(h, hipMemsetAsync(a.prune, 0, PRUNE_HDR_WORDS * sizeof(unsigned long long), h->stream));
+  const PruneLaunch pl{0, 0, 8, h->d_xc32.as<float>(), h->d_pre.as<double>(), dm, de};
+  HIPCHK(h, by_kind(launch_prescreen_kinds, h->kind)(h->stream, a, std::min<int64_t>(nblk, 2 * (int64_t)h->num_cu), pl));
+  if (int rc = stage_out_finish(h, dm, mean32, M, where)) return rc;
+  if (int rc = stage_out_finish(h, de, E, M, where)) return rc;
+  return finish(h);
 }
 
 // ---- expected hypervolume improvement (tgp_kernels_ehvi.hip) ----------------------------------------------------

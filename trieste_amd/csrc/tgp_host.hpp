@@ -130,6 +130,7 @@ struct tgp_handle_s {
   int wq_planes = 0;
   // model state on device
   DevBuf d_xc, d_xn, d_ls, d_X, d_Y, d_Xs, d_A, d_L, d_W, d_alpha, d_err, d_tmp1, d_tmp2, d_info;
+  DevBuf d_xc32, d_pre;   // the float32 pre-screen of the pruned EI arg-max (PruneLaunch::xc32 / pre), written at `update`
   // local penalization applied to every tgp_acq_* result while pen_kind != 0 (tgp_set_penalization)
   int pen_kind = 0, pen_P = 0;
   DevBuf d_pen;  // [P, d] pending points, [P] radius, [P] scale

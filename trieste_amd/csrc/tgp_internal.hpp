@@ -133,10 +133,13 @@ struct SweepArgs {
 // Models of more than one row block run in three phases and keep more behind the same pointer:
 //   PRUNE_W_SURVIVORS S      PRUNE_W_ITEMS  split work items (0: whole-block regime)      PRUNE_W_GROUPS  ranges per survivor
 //   PRUNE_W_IB ..     the range boundaries
+//   PRUNE_W_PREBEST   phase 0 (the float32 pre-screen): the bits of the largest lower seed eta - mean32 - E, rounded down; it is
+//                     never above what PRUNE_W_BEST ends at      PRUNE_W_PRESCREENED  blocks whose exact mean pass was skipped
 // and from word PRUNE_HDR_WORDS on the areas of PruneView.  Only the header is cleared per launch: everything else is
 // written before it is read.
 constexpr int PRUNE_W_BEST = 0, PRUNE_W_GIVEN_UP = 1, PRUNE_W_SKIPPED = 2, PRUNE_W_SCREENED = 3, PRUNE_W_DRAW = 4,
-              PRUNE_W_SURVIVORS = 5, PRUNE_W_ITEMS = 6, PRUNE_W_GROUPS = 7, PRUNE_W_IB = 16, PRUNE_MAX_GROUPS = 64,
+              PRUNE_W_SURVIVORS = 5, PRUNE_W_ITEMS = 6, PRUNE_W_GROUPS = 7, PRUNE_W_PREBEST = 8, PRUNE_W_PRESCREENED = 9,
+              PRUNE_W_IB = 16, PRUNE_MAX_GROUPS = 64,
               PRUNE_HDR_WORDS = 128;
 constexpr size_t PRUNE_DUMP_BLOCK = 32 * 1024;                   // doubles per (survivor, row block): 256 KiB
 constexpr size_t PRUNE_DUMP_MAX_BYTES = (size_t)1 << 30;         // the dump area never exceeds this, nor the launch's K* slabs
@@ -184,7 +187,17 @@ struct PruneLaunch {
   int max_survivors;   // split cap on S after clamping (0: never split); the dump area holds this many survivors
   int max_groups;      // cap on ranges per survivor (0: up to the row blocks)
   int mean_waves;      // phase 1: waves per SIMD it is compiled for (8 or 4)
+  // phase 0, the float32 pre-screen (null xc32: off).  Both arrays belong to the model and are written once at `update`
+  // (launch_prescreen_prep); they travel here and not in ModelDev, whose layout every sweep kernel's arguments share
+  const float* xc32;   // [Npad][dp] float32 copy of sqrt(SCALE) (Xs - Xs_0), SCALE of TrajShape<kind>
+  const double* pre;   // [PRE_WORDS]: see PRE_*
+  // the read-back of tgp_prescreen_means (null in the arg-max): per candidate the device's mean32 and its bound E
+  double *m32_out, *e_out;
 };
+// PruneLaunch::pre: |alpha|_1; the largest sqrt(SCALE) |Xs_k - Xs_0|_2 over the training rows; sqrt(SCALE) |Xs_0|_2;
+// sqrt(SCALE) itself
+constexpr int PRE_ALPHA_L1 = 0, PRE_XC_MAX = 1, PRE_X0 = 2, PRE_RS = 3, PRE_WORDS = 4;
+void launch_prescreen_prep(hipStream_t s, const ModelDev& m, float* xc32, double* pre);
 constexpr double I8_TIGHT = 1.0078125;  // digit-plane scales S_i = I8_TIGHT max_k |W_ik|, S' = I8_TIGHT variance: the
                                         // balanced digits reach |q| <= 0x7f7f7f7f = 0.99609 2^31 > 2^31 / I8_TIGHT
 constexpr int64_t I8_CANARY_PERIOD = 4096;  // one sampled candidate in 4096 (a power of two)
@@ -242,6 +255,8 @@ int64_t sweep_grid(const SweepArgs& a, bool joint);
 TGP_KIND_FAMILY(launch_sweep_kind, hipStream_t, const SweepArgs&, bool joint, int64_t grid);
 TGP_KIND_FAMILY(launch_sweep_dma_kind, hipStream_t, const SweepArgs&, int64_t grid);
 TGP_KIND_FAMILY(launch_sweep_prune_kind, hipStream_t, const SweepArgs&, int64_t grid, const PruneLaunch&);
+// phase 0 alone over every block of `a` (bounds, PRUNE_W_PREBEST, and the read-back arrays of `pl`): tgp_prescreen_means
+TGP_KIND_FAMILY(launch_prescreen_kind, hipStream_t, const SweepArgs&, int64_t grid, const PruneLaunch&);
 TGP_KIND_FAMILY(launch_joint_kind, hipStream_t, const SweepArgs&, int64_t grid);
 TGP_KIND_FAMILY(launch_sweep_i8_kind, hipStream_t, const SweepArgs&, int64_t grid, int planes);
 template <typename F>

@@ -849,6 +849,54 @@ void launch_centred_rows(hipStream_t s, const double* Xs, double* xc, double* xn
   hipLaunchKernelGGL(centred_rows_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, s, Xs, xc, xn, Npad, dp);
 }
 
+// What the float32 pre-screen of the pruned EI arg-max (tgp_kernels_sweep_dma.inc, phase 0) reads, written once per
+// `update` by one workgroup: xc32 = float32(rs xc) with rs = sqrt(SCALE) of TrajShape<kind> (the pre-screen's squared
+// distance is the shape's argument q, no multiplication per entry; padding rows are ZERO so that their entries stay finite
+// beside alpha = 0) and pre[PRE_*]: |alpha|_1, the largest rs |xc_k|_2 over the training rows, rs |Xs_0|_2, rs.  Fixed
+// summation order: the bound E that follows from them is a function of the model alone.
+__global__ __launch_bounds__(1024) void prescreen_prep_kernel(ModelDev m, double rs, float* __restrict__ xc32,
+                                                              double* __restrict__ pre) {
+  __shared__ double red[2][16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t n = m.Npad * m.dp;
+  for (int64_t e = tid; e < n; e += 1024) xc32[e] = (e / m.dp < m.N) ? (float)(rs * m.xc[e]) : 0.0f;
+  double l1 = 0.0, xmax = 0.0;
+  for (int64_t k = tid; k < m.N; k += 1024) {
+    l1 += fabs(m.alpha[k]);
+    const double v = m.xn[k];
+    xmax = (v > xmax || v != v) ? v : xmax;   // (a NaN norm stays: the bound must not come out finite)
+  }
+  l1 = wave_sum(l1);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double o = __shfl_xor(xmax, off, 64);
+    xmax = (o > xmax || o != o) ? o : xmax;
+  }
+  if (lane == 0) {
+    red[0][w] = l1;
+    red[1][w] = xmax;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    l1 = 0.0;
+    xmax = 0.0;
+    for (int i = 0; i < 16; ++i) {
+      l1 += red[0][i];
+      xmax = (red[1][i] > xmax || red[1][i] != red[1][i]) ? red[1][i] : xmax;
+    }
+    double x0 = 0.0;
+    for (int c = 0; c < m.dp; ++c) x0 = fma(m.Xs[c], m.Xs[c], x0);
+    pre[PRE_ALPHA_L1] = l1;
+    pre[PRE_XC_MAX] = rs * sqrt(xmax);
+    pre[PRE_X0] = rs * sqrt(x0);
+    pre[PRE_RS] = rs;
+  }
+}
+void launch_prescreen_prep(hipStream_t s, const ModelDev& m, float* xc32, double* pre) {
+  const double rs = with_kind(m.kind, [](auto K) { return std::sqrt(TrajShape<decltype(K)::value>::SCALE); });
+  hipLaunchKernelGGL(prescreen_prep_kernel, dim3(1), dim3(1024), 0, s, m, rs, xc32, pre);
+}
+
 // one wave per row: y[i] = sum_{k in tri range} M[i][k] x[k].  The row is walked from a 16-byte aligned start
 // (entries outside the triangle are explicit zeros in both users, W and Wt) with two entries per lane and load and
 // four independent partial sums, so that eight loads per lane are in flight instead of one dependent chain.

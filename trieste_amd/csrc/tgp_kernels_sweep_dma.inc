@@ -126,6 +126,8 @@ constexpr int D_PRUNE_LDS = 5 * DBN + 3;   // [4][128] checkpoint norms, [128] m
 constexpr double PRUNE_MIN_BEST = 1e-280, PRUNE_MARGIN = 1.0 + 0x1p-14;
 constexpr int PRUNE_NO_SCREEN = 1, PRUNE_STATIC_BLOCKS = 2;   // SweepArgs::prune_flags (tgp_set_variant bits 12, 13)
 // Models of more than one row block run the pruned arg-max in THREE PHASES on one stream (DESIGN.md 4.1):
+//   0 prune_prescreen_kernel: every block's mean in float32 with a bound that holds by construction; phase 1 skips what
+//     that dismisses (below; tgp_set_variant bit 14 runs without it);
 //   1 prune_mean_kernel: the mean pass of every block -- means, seed, and the block's largest bound at the prior variance;
 //     prune_list_kernel then applies the give-up rule per block against the best word that holds EVERY seed and writes the
 //     survivors in block order (S and the order of the work are deterministic), the regime and the ranges;
@@ -569,6 +571,161 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
 }
 
 #ifdef TGP_SWEEP_PRUNE_TU
+// ---- Phase 0: the float32 pre-screen (nb > 1; DESIGN.md 4.1 has the derivation) ----------------------------------------------
+// Phase 1 spends its time (float64 distance, software sqrt and exp per K* entry) on blocks of which all but a handful are
+// given up by the mean screen; all the screen needs of their means is a bound.  Phase 0 forms every candidate's mean in
+// float32 kernel arithmetic, mean32, with a bound |mean32 - mean| <= E that holds by construction, and leaves per block
+//   bounds()[blk] = ub32: the largest tail at (mean32 - E, prior variance), inflated past the tail's own resolution -- never
+//                   below the bound phase 1 would store (EI falls with the mean; +inf where mean32 or E is not finite);
+//   PRUNE_W_PREBEST: the largest eta - mean32 - E, rounded down -- never above the top seed eta - mean.
+// Phase 1 skips a block whose ub32 MARGIN < prebest.  Why results, S and every counter keep their bits:
+//   * the block B* of the top seed has ub32 >= ub >= seed (1 - 1e-5) (the seed argument above), so
+//     ub32 MARGIN > seed >= prebest: it is never skipped and PRUNE_W_BEST ends at the value it had without phase 0;
+//   * a skipped block has ub MARGIN <= ub32 MARGIN < prebest <= best: prune_list_kernel drops it (it reads ub32 where the
+//     exact bound stood) exactly as it dropped it on the exact bound -- same list, same S, same counters;
+//   * the means of a skipped block are never read: only listed blocks' are.
+// Per entry: q = SCALE r^2 by the difference form on float32 copies of the centred, sqrt(SCALE)-scaled coordinates (centred
+// and scaled in float64, then rounded: a shift of the whole box costs nothing), the shape by v_sqrt_f32 / v_exp_f32 (the
+// square root IS the base-2 exponent, TrajShape), the value converted and folded by a float64 fma against alpha (the sum
+// adds no term that grows with N).  The bound, with u = 2^-24, S = |a|_2 + max_k |b_k|_2 (a, b the scaled centred
+// candidate and rows) and G1 = sup 2 sqrt(q) |f'(q)|, G2 = sup q |f'(q)| of the shape f:
+//   |q32 - q| <= 2 u sqrt(q) S + (2 DP + 2) u q      (two conversions and the subtraction; DP fmas or 2 DP mul / adds)
+//   |f32 - f| <= u [G1 S + G2 (2 DP + 10) + 10]      (+ 8 u q: v_sqrt_f32 at 2 ulp; 10 u: v_exp_f32 at 2 ulp, the
+//                                                     polynomial's two constants and two fmas, the product)
+//   E = |alpha|_1 variance (1.0625 u [..] + 2^-53 [2 G1 (|Xs_0| + S) + 256 + Npad] + 2^-60) + 2^-50 (|mean32| + |eta|)
+// (1/16 for the second-order terms; the 2^-53 term for the float64 side -- centring, the exact pass's own rounding; 2^-60
+// for flushed float32 denormals: at most DP squares below 2^-126 are lost, 2^-61 on sqrt(q); the last term for the
+// roundings of mean32 - E and eta - mean32).  A block with a candidate whose E is not finite or exceeds the variance, or
+// whose mean32 is not finite, gets +inf and posts no lower seed.
+template <int KIND>
+struct PreShape {
+  static constexpr double G1 = KIND == KIND_RBF ? 0.72 : KIND == KIND_M12 ? 0.70 : KIND == KIND_M32 ? 0.26 : 0.20;
+  static constexpr double G2 = KIND == KIND_RBF ? 0.37 : KIND == KIND_M12 ? 0.19 : KIND == KIND_M32 ? 0.28 : 0.31;
+};
+constexpr double PRE_TAIL_INFLATE = 1.0 + 4e-5, PRE_MIN_BOUND = 1e-290;   // (below PRUNE_MIN_BEST: a floor skips nothing new)
+
+template <int KIND>
+__device__ __forceinline__ float prescreen_shape(float q) {   // q = SCALE r^2 >= 0 (difference form)
+  if constexpr (KIND == KIND_RBF) {
+    return __builtin_amdgcn_exp2f(-q);
+  } else {
+    constexpr float IL = (float)(1.0 / TrajShape<KIND>::L2E), IL2 = (float)(1.0 / (3.0 * TrajShape<KIND>::L2E * TrajShape<KIND>::L2E));
+    const float qc = fmaxf(q, (float)TrajShape<KIND>::FLOOR);
+    const float v = __builtin_amdgcn_sqrtf(qc);
+    const float e = __builtin_amdgcn_exp2f(-v);
+    if constexpr (KIND == KIND_M12) return e;
+    else if constexpr (KIND == KIND_M32) return fmaf(IL, v, 1.0f) * e;
+    else return fmaf(IL2, qc, fmaf(IL, v, 1.0f)) * e;
+  }
+}
+
+// the bound E of a candidate whose scaled centred norm is `an` and whose float32 mean is m32
+template <int KIND, int DP>
+__device__ __forceinline__ double prescreen_bound(const SweepArgs& a, const double* pre, double an, double m32) {
+  const double S = an + pre[PRE_XC_MAX];
+  const double c32 = 1.0625 * 0x1p-24 * (PreShape<KIND>::G1 * S + PreShape<KIND>::G2 * (2 * DP + 10) + 10.0);
+  const double c64 = 0x1p-53 * (2.0 * PreShape<KIND>::G1 * (pre[PRE_X0] + S) + 256.0 + (double)a.m.Npad);
+  return pre[PRE_ALPHA_L1] * a.m.variance * (c32 + c64 + 0x1p-60) + 0x1p-50 * (fabs(m32) + fabs(a.acq_param));
+}
+
+template <int KIND, int DP>
+__global__ __launch_bounds__(1024, 8) void prune_prescreen_kernel(const SweepArgs a, const PruneLaunch pl) {
+  __shared__ float xqs[DP * DBN];     // [DP][128] centred, scaled candidate coordinates
+  __shared__ double mred[8 * DBN];    // [8][128]
+  __shared__ double ubw[2], sdw[2];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kcol = tid & 127;
+  const int krg = __builtin_amdgcn_readfirstlane(tid >> 7);   // row group: rows 32 g + 4 krg .. + 3
+  const int d = a.m.d;
+  const int ng = (int)(a.m.Npad / 32);
+  const double variance = a.m.variance;
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  const PruneView pv{a.prune, nblk};
+  const double rs = pl.pre[PRE_RS];
+  typedef const __attribute__((address_space(4))) float* cfptr;
+  const cfptr xc32 = (cfptr)(const __attribute__((address_space(1))) float*)(pl.xc32);
+  for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    for (int e = tid; e < DBN * DP; e += 1024) {
+      const int j = e / DP, c = e % DP;
+      const int64_t cand = blk * DBN + j;
+      const int64_t src = cand < a.M ? cand : 0;
+      // centred in float64 FIRST (Xs_0 is row 0 of Xs), then rounded
+      xqs[c * DBN + j] = (c < d) ? (float)(rs * (a.Xq[src * d + c] / as_const(a.m.ls)[c] - as_const(a.m.Xs)[c])) : 0.0f;
+    }
+    __syncthreads();
+    float xr[DP];
+#pragma unroll
+    for (int c = 0; c < DP; ++c) xr[c] = xqs[c * DBN + kcol];
+    double macc = 0.0;
+    for (int g = 0; g < ng; ++g) {
+      const int64_t krow0 = (int64_t)g * 32 + 4 * krg;
+      const cfptr xs = xc32 + krow0 * DP;
+      const cptr al = as_const(a.m.alpha + krow0);
+      float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float t0 = xr[c] - xs[r * DP + c];
+          q[r] = fmaf(t0, t0, q[r]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) macc = fma((double)prescreen_shape<KIND>(q[r]), al[r], macc);
+    }
+    mred[krg * 128 + kcol] = macc;
+    __syncthreads();
+    if (tid < 128) {
+      double sum = 0.0;
+#pragma unroll
+      for (int g = 0; g < 8; ++g) sum += mred[g * 128 + tid];
+      const double m32 = fma(variance, sum, a.m.mean_const);
+      const int64_t cand = blk * DBN + tid;
+      const bool valid = cand < a.M;
+      double ub = -INFINITY, seed = 0.0;   // columns past M have nothing to lose
+      if (valid) {
+        double an = 0.0;
+        for (int c = 0; c < d; ++c) {
+          const double v = rs * (a.Xq[cand * d + c] / as_const(a.m.ls)[c] - as_const(a.m.Xs)[c]);
+          an = fma(v, v, an);
+        }
+        const double E = prescreen_bound<KIND, DP>(a, pl.pre, sqrt(an), m32);
+        if (pl.m32_out) {
+          pl.m32_out[cand] = m32;
+          pl.e_out[cand] = E;
+        }
+        ub = INFINITY;
+        if (E <= variance && fabs(m32) < INFINITY) {   // (a NaN compares false)
+          const double t = acq_tail(ACQ_EI, a.acq_param, m32 - E, fmax(variance, VAR_FLOOR), a.m.noise);
+          if (!(t != t)) ub = fmax(t * PRE_TAIL_INFLATE, PRE_MIN_BOUND);
+          seed = ((a.acq_param - m32) - E) * (1.0 - 0x1p-50);   // rounded down
+          if (!(seed > 0.0)) seed = 0.0;
+        }
+      }
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        ub = fmax(ub, __shfl_xor(ub, o, 64));
+        seed = fmax(seed, __shfl_xor(seed, o, 64));
+      }
+      if (lane == 0) {
+        ubw[w] = ub;
+        sdw[w] = seed;
+      }
+    }
+    __syncthreads();   // xqs and mred are rewritten by the next block
+    if (tid == 0) {
+      const double ub = fmax(ubw[0], ubw[1]);
+      pv.bounds()[blk] = ub;
+      const double seed = fmax(sdw[0], sdw[1]);
+      // (one candidate without a finite bound takes the block's lower seed with it)
+      if (ub < INFINITY && seed > 0.0) atomicMax(a.prune + PRUNE_W_PREBEST, (unsigned long long)__double_as_longlong(seed));
+    }
+  }
+}
+#endif
+
+#ifdef TGP_SWEEP_PRUNE_TU
 // Phase 1: the mean pass of every candidate block, blocks i, i + #WG, ... (a pass costs the same for every block).  Leaves
 // the block's 128 means, posts its seed as the fused kernel did and stores the largest EI tail at the prior variance over
 // its valid candidates (a NaN bound as +inf: never screened).  Gives nothing up.  No A / B stages, no accumulators, no
@@ -588,7 +745,15 @@ __global__ __launch_bounds__(1024, WAVES) void prune_mean_kernel(const SweepArgs
   const int64_t nblk = (a.M + DBN - 1) / DBN;
   const PruneView pv{a.prune, nblk};
   const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN);
+  // phase 0 (zero when it did not run): written by the launch in front of this one, stable during this one
+  const double prebest = __longlong_as_double((long long)a.prune[PRUNE_W_PREBEST]);
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    // a block the pre-screen dismissed keeps its float32 bound and costs nothing here (one decision per workgroup; thread 0
+    // rewrites the word only at the end of a block that was not skipped)
+    if (prebest > PRUNE_MIN_BEST && pv.bounds()[blk] * PRUNE_MARGIN < prebest) {
+      if (tid == 0) atomicAdd(a.prune + PRUNE_W_PRESCREENED, 1ull);
+      continue;
+    }
     for (int e = tid; e < DBN * DP; e += 1024) scale_entry(xqs, a.Xq, a.M, a.m.d, a.m.ls, blk, e / DP, e % DP);
     __syncthreads();
     double macc = 0.0;
@@ -626,7 +791,9 @@ __global__ __launch_bounds__(1024) void prune_list_kernel(const SweepArgs a, con
   const PruneView pv{a.prune, nblk};
   const double* ubs = pv.bounds();
   int64_t* list = pv.list();
-  const double best = __longlong_as_double((long long)a.prune[PRUNE_W_BEST]);
+  // (the pre-screen's lower seed never exceeds the best word -- phase 0 above; the larger of the two is the best word)
+  const double best = fmax(__longlong_as_double((long long)a.prune[PRUNE_W_BEST]),
+                           __longlong_as_double((long long)a.prune[PRUNE_W_PREBEST]));
   const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN) && best > PRUNE_MIN_BEST;
   int64_t base = 0;
   for (int64_t c0 = 0; c0 < nblk; c0 += 1024) {
@@ -708,6 +875,10 @@ __global__ __launch_bounds__(1024) void prune_fold_kernel(const SweepArgs a) {
 }
 
 template <int KIND, int DP>
+void launch_prune_prescreen(hipStream_t s, const SweepArgs& a, int64_t wg, const PruneLaunch& pl) {
+  hipLaunchKernelGGL((prune_prescreen_kernel<KIND, DP>), dim3((unsigned)wg), dim3(1024), 0, s, a, pl);
+}
+template <int KIND, int DP>
 void launch_prune_mean(hipStream_t s, const SweepArgs& a, int64_t wg, int waves) {
   if (waves >= 8) hipLaunchKernelGGL((prune_mean_kernel<KIND, DP, 8>), dim3((unsigned)(2 * wg)), dim3(1024), 0, s, a);
   else hipLaunchKernelGGL((prune_mean_kernel<KIND, DP, 4>), dim3((unsigned)wg), dim3(1024), 0, s, a);
@@ -736,6 +907,7 @@ hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) 
 hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid, const PruneLaunch& pl) {
   if (a.m.Npad / DBM <= 1) return launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
   hipError_t e = with_dp<16>(a.m.dp, [&](auto DP) {
+    if (pl.xc32) launch_prune_prescreen<TGP_SWEEP_KIND, DP()>(s, a, 2 * grid, pl);   // two workgroups per compute unit
     launch_prune_mean<TGP_SWEEP_KIND, DP()>(s, a, grid, pl.mean_waves);
     return hipSuccess;
   });
@@ -745,6 +917,12 @@ hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const
   if (e != hipSuccess) return e;
   if (pl.max_survivors > 0) hipLaunchKernelGGL(prune_fold_kernel, dim3((unsigned)pl.max_survivors), dim3(1024), 0, s, a);
   return hipGetLastError();
+}
+hipError_t TGP_CAT(launch_prescreen_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid, const PruneLaunch& pl) {
+  return with_dp<16>(a.m.dp, [&](auto DP) {
+    launch_prune_prescreen<TGP_SWEEP_KIND, DP()>(s, a, grid, pl);
+    return hipGetLastError();
+  });
 }
 #else
 hipError_t TGP_CAT(launch_sweep_dma_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid) {

@@ -585,6 +585,24 @@ def prune_screened(eng: "GPEngine"):
     return s.value
 
 
+def prune_prescreened(eng: "GPEngine"):
+    """Of the blocks the mean screen gave up in ``eng``'s most recent arg-max, those the float32 pre-screen dismissed before
+    their float64 mean pass (tgp_get_prune_prescreened).  Synchronises the engine's stream."""
+    s = C.c_int64()
+    eng._chk(eng._lib.tgp_get_prune_prescreened(eng._h, C.byref(s)))
+    return s.value
+
+
+def prescreen_means(eng: "GPEngine", Xq):
+    """(mean32, E) per candidate: the posterior mean as the pre-screen forms it on the device and the bound it holds for
+    |mean32 - mean| (tgp_prescreen_means).  A test and measurement aid."""
+    a, lead, M = eng._flat(Xq)
+    m32, pm = eng._out(a, lead)
+    E, pe = eng._out(a, lead)
+    eng._chk(eng._lib.tgp_prescreen_means(eng._h, a.ptr, M, pm, pe, a.where))
+    return m32, E
+
+
 def set_prune_split(eng: "GPEngine", max_survivors: int = -1, max_groups: int = 0):
     """The split regime of the pruned EI sweep (tgp_set_prune_split): blocks that survive the mean screen are cut into
     ranges of row blocks when at most ``max_survivors`` survive (-1: the derived cap, 0: never), into at most
