@@ -325,15 +325,33 @@ int tgp_batch_ei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, co
  *   tgp_ehvi_argmax: the same followed by the arg-max over the values (one trip of 8 B per candidate through device memory, as
  *     the penalised and entropy tails); conventions of tgp_acq_argmax: host outputs, the first index wins ties, M < 1 is
  *     TGP_ERR_SHAPE.
- *   tgp_ehvi_last_ms: of the most recent of the three calls above on this (leading) handle: the summed times of the P
- *     posterior sweeps (what tgp_last_kernel_ms reports after tgp_ehvi_values / _argmax; 0 for the small-product path and for
- *     tgp_ehvi_moments) and the time of the tail kernel. */
+ *   tgp_ehvi_moments_grad: tgp_ehvi_moments with the adjoints of the moments: val [M], gmean and gvar [P,M] objective-major,
+ *         gmean_j = -sum_cells (prod_{i != j} D_i) (cdf(z_u) - cdf(z_l)),
+ *         gvar_j  = (1 / (2 s_j)) sum_cells (prod_{i != j} D_i) (pdf(z_u) - pdf(z_l)),   D_i = max(g_i(ub_i) - g_i(lb_i), 0)
+ *     (d g / d m = -cdf(z), d g / d s = pdf(z)).  The derivative is that of the function as computed: an objective of a cell
+ *     whose factor the max clipped to zero contributes none, and cdf and pdf are exactly 0 at a bound clipped to -1e10.  var is
+ *     taken as given (no clip rule).  The tile is narrower than the value kernel's (the largest power of two <= 8 with
+ *     24 P V C <= 160 KiB: the call serves the tens to 2048 points of an L-BFGS-B iteration) and so is the summation order over
+ *     the cells: val agrees with tgp_ehvi_moments to rounding, not in bits.  Errors as tgp_ehvi_moments.
+ *   tgp_ehvi_value_grad: Xq [M,d] -> val [M], grad [M,d], 1 <= M <= 2048 (else TGP_ERR_SHAPE: callers chunk, as for
+ *     tgp_joint_vjp); handle checks of tgp_ehvi_values.  Per handle K*^T and W K* by the small product and the small-predict
+ *     tail (float64 whatever tgp_set_precision says, as tgp_acq_value_grad), the moments stacked on the leading handle, the
+ *     gradient tail (gvar_j = 0 where handle j's variance was clipped at 1e-12), per handle the posterior's vector-Jacobian
+ *     product on that handle's own K*^T and W K* with (gmean_j, gvar_j) as adjoints, and the P gradients added in the order
+ *     j = 0 .. P-1.  Each handle's work runs on its own stream, ordered against the leading handle's by events; ONE host
+ *     synchronisation, of the leading handle's stream, by which time every member's work has completed.
+ *   tgp_ehvi_last_ms: of the most recent of the five calls above on this (leading) handle: the summed times of the P
+ *     posterior sweeps (what tgp_last_kernel_ms reports after tgp_ehvi_values / _argmax; 0 for the small-product path, for
+ *     tgp_ehvi_moments, tgp_ehvi_moments_grad and tgp_ehvi_value_grad) and the time of the tail kernel. */
 int tgp_set_ehvi_partition(tgp_handle h, int P, const double* bounds, int bounds_stride, const int* n_bounds,
                            const int32_t* lower_idx, const int32_t* upper_idx, int64_t K);
 int tgp_ehvi_moments(tgp_handle h, const double* mean, const double* var, int64_t M, double* out, int where);
 int tgp_ehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t M, double* out, int where);
 int tgp_ehvi_argmax(const tgp_handle* hs, int P, const double* Xq, int64_t M, int64_t index_base, double* best_val,
                     int64_t* best_idx, double* best_x, int where);
+int tgp_ehvi_moments_grad(tgp_handle h, const double* mean, const double* var, int64_t M, double* val, double* gmean,
+                          double* gvar, int where);
+int tgp_ehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t M, double* val, double* grad, int where);
 int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms);
 
 /* == BatchReparametrizationSampler.sample (sampler.py:208-287) itself: out [G,S,q] = mean +

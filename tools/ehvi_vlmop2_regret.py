@@ -3,7 +3,11 @@ ExpectedHypervolumeImprovement for 20 steps, log10 hypervolume regret per step a
 reference point [1.1, 1.1] (the reference asserts < -3.65 with a fitted GPflow model and L-BFGS-B refinement of the acquisition,
 tests/integration/test_multi_objective_bayesian_optimization.py:54-73,173-185; nothing is asserted here).
 
-    python tools/ehvi_vlmop2_regret.py      -> profiles/r13_ehvi_vlmop2_regret.txt"""
+    python tools/ehvi_vlmop2_regret.py                    -> profiles/r13_ehvi_vlmop2_regret.txt, r20_ehvi_vlmop2_regret.txt
+    python tools/ehvi_vlmop2_regret.py --differentiable   -> profiles/r20_ehvi_vlmop2_regret_refined.txt
+
+The second form builds the function with ``value_and_gradient``, which the default optimizer refines by L-BFGS-B; both start
+from the same data and seed."""
 import os
 import sys
 import time
@@ -19,6 +23,7 @@ from trieste_amd.ask_tell_optimization import AskTellOptimizer
 from trieste_amd.data import Dataset
 from trieste_amd.space import Box
 
+differentiable = "--differentiable" in sys.argv[1:]
 trieste_amd.set_seed(1234)
 space = Box([-2.0, -2.0], [2.0, 2.0])
 x = space.sample_sobol(10, skip=0)
@@ -26,11 +31,13 @@ data = Dataset(x, OBJ.vlmop2(x, 2))
 members = [M.GaussianProcessRegression(M.build_gpr(Dataset(x, data.observations[:, j:j + 1]), space, likelihood_variance=1e-5))
            for j in range(2)]
 stack = M.TrainableModelStack(*[(m, 1) for m in members])
-opt = AskTellOptimizer(space, data, stack, EfficientGlobalOptimization(ExpectedHypervolumeImprovement()))
+builder = ExpectedHypervolumeImprovement(differentiable=differentiable)
+opt = AskTellOptimizer(space, data, stack, EfficientGlobalOptimization(builder))
 ref = np.array([1.1, 1.1])
 t = 1.0 / np.sqrt(2.0)
 line = np.linspace(-t, t, 1000)[:, None] * np.ones((1, 2))
 ideal = Pareto(OBJ.vlmop2(line, 2)).hypervolume_indicator(ref)
+print(f"{builder!r}, default optimizer")
 t0 = time.perf_counter()
 for step in range(20):
     q = opt.ask()

@@ -67,6 +67,8 @@ SIGNATURES = {
     "tgp_ehvi_moments": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int]),
     "tgp_ehvi_values": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, C.c_int]),
     "tgp_ehvi_argmax": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _dp, _ip, _vp, C.c_int]),
+    "tgp_ehvi_moments_grad": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int]),
+    "tgp_ehvi_value_grad": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_int]),
     "tgp_ehvi_last_ms": (C.c_int, [_vp, _dp, _dp]),
     "tgp_reparam_samples": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int]),
     "tgp_traj_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),

@@ -19,7 +19,8 @@ from .interface import (AcquisitionFunctionBuilder, AcquisitionFunctionClass, Gr
                         SingleModelAcquisitionBuilder, SingleModelGreedyAcquisitionBuilder,
                         SingleModelVectorizedAcquisitionBuilder, VectorizedAcquisitionFunctionBuilder)
 from .multi_objective import (DividedAndConquerNonDominated, ExactPartition2dNonDominated, ExpectedHypervolumeImprovement,
-                              Pareto, expected_hv_improvement, get_reference_point, non_dominated,
+                              Pareto, differentiable_expected_hv_improvement, expected_hv_improvement,
+                              get_reference_point, non_dominated,
                               prepare_default_non_dominated_partition_bounds)
 from .optimizer import (FailedOptimizationError, automatic_optimizer_selector, batchify_joint, batchify_vectorize,
                         generate_continuous_optimizer, generate_initial_points, generate_random_search_optimizer,

@@ -3,7 +3,7 @@ set with its hypervolume indicator, the partitions of the non-dominated region i
 improvement over a stack of engine-backed models.  The partitions are host arithmetic (numpy) on a few dozen front points;
 the acquisition function itself runs on the device (tgp_ehvi_*)."""
 from .dominance import non_dominated
-from .ehvi import ExpectedHypervolumeImprovement, expected_hv_improvement
+from .ehvi import ExpectedHypervolumeImprovement, differentiable_expected_hv_improvement, expected_hv_improvement
 from .pareto import Pareto, get_reference_point
 from .partition import (DividedAndConquerNonDominated, ExactPartition2dNonDominated,
                         prepare_default_non_dominated_partition_bounds)

@@ -1116,7 +1116,10 @@ int tgp_create(int device_id, int d, int kernel_kind, tgp_handle* out) {
   h->dp = dpad_of(d);
   h->kind = kernel_kind;
   if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipEventCreate(&h->ev0)) != hipSuccess ||
-      (e = hipEventCreate(&h->ev1)) != hipSuccess) {
+      (e = hipEventCreate(&h->ev1)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming)) != hipSuccess) {
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
     delete h;
     return fail(nullptr, TGP_ERR_HIP, "device init failed: %s", hipGetErrorString(e));
   }
@@ -1150,6 +1153,7 @@ int tgp_destroy(tgp_handle h) {
   if (h->rep_host) (void)hipHostFree(h->rep_host);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
+  if (h->ev_order) (void)hipEventDestroy(h->ev_order);
   delete h;
   (void)hipGetLastError();  // do not leave a cleanup error behind for the thread's next launch check
   return TGP_OK;
@@ -3221,10 +3225,20 @@ void ehvi_read_tail_ms(tgp_handle h) {
   (void)hipGetLastError();
 }
 
-// checks of the stack, the candidates staged once on the leading handle, and every member's (mean, clipped var) through
-// tgp_predict itself into the leading handle's scratch: *dmean [P][M], *dvar [P][M]
-int ehvi_stack_moments(const tgp_handle* hs, int P, const double* Xq, int64_t M, int where, const double** dXq_out,
-                       double** dmean, double** dvar) {
+// the gradient tail likewise: dval [M], dgm / dgv [P][M]
+int ehvi_enqueue_grad_tail(tgp_handle h, const double* dmean, const double* dvar, int64_t M, int zero_clipped, double* dval,
+                           double* dgm, double* dgv) {
+  const double* db = h->d_ehvi.as<double>();
+  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_ehvi_grad_tail(h->stream, h->ehvi_P, h->ehvi_V, h->ehvi_nb, db, dc, h->ehvi_K, dmean, dvar, M, zero_clipped, dval, dgm,
+                        dgv);
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return TGP_OK;
+}
+
+// checks of the stack: errors are reported on the leading handle
+int ehvi_check_stack(const tgp_handle* hs, int P) {
   tgp_handle h = hs[0];
   if (P < 2 || P > EHVI_MAX_P)
     return fail(h, TGP_ERR_SHAPE, "expected hypervolume improvement takes 2..%d objectives, got %d", EHVI_MAX_P, P);
@@ -3239,6 +3253,15 @@ int ehvi_stack_moments(const tgp_handle* hs, int P, const double* Xq, int64_t M,
     return fail(h, TGP_ERR_ARG, "the partition has %d objectives, the stack %d", h->ehvi_P, P);
   for (int j = 0; j < P; ++j)
     if (!hs[j]->have_data) return fail(h, TGP_ERR_STATE, "model %d of the stack has no data: call tgp_set_data first", j);
+  return TGP_OK;
+}
+
+// those checks, the candidates staged once on the leading handle, and every member's (mean, clipped var) through
+// tgp_predict itself into the leading handle's scratch: *dmean [P][M], *dvar [P][M]
+int ehvi_stack_moments(const tgp_handle* hs, int P, const double* Xq, int64_t M, int where, const double** dXq_out,
+                       double** dmean, double** dvar) {
+  tgp_handle h = hs[0];
+  if (int rc = ehvi_check_stack(hs, P)) return rc;
   if (M == 0) return TGP_OK;  // (an empty call has run the checks)
   if (!Xq) return fail(h, TGP_ERR_ARG, "Xq is NULL");
   if (int rc = set_device(h)) return rc;
@@ -3333,6 +3356,115 @@ int tgp_ehvi_argmax(const tgp_handle* hs, int P, const double* Xq, int64_t M, in
   h->last_ms = h->ehvi_sweep_ms;
   h->last_launches = P;
   return w.give(h, Xq, dXq, M, index_base, where, best_val, best_idx, best_x);
+}
+
+int tgp_ehvi_moments_grad(tgp_handle h, const double* mean, const double* var, int64_t M, double* val, double* gmean,
+                          double* gvar, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = ehvi_need_partition(h)) return rc;
+  if (M < 0) return fail(h, TGP_ERR_SHAPE, "M must be >= 0");
+  if (M == 0) return TGP_OK;
+  if (!mean || !var || !val || !gmean || !gvar) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  // host residency: the moments through s_out1 / s_out2 as in tgp_ehvi_moments, the value through s_out3, the two adjoints
+  // through s_in and s_ent (idle in a call on given moments)
+  const size_t pm = (size_t)h->ehvi_P * M;
+  const double *dmean, *dvar;
+  double *dval, *dgm, *dgv;
+  if (int rc = stage_in(h, h->s_out1, mean, pm, where, &dmean)) return rc;
+  if (int rc = stage_in(h, h->s_out2, var, pm, where, &dvar)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out3, val, M, where, &dval)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_in, gmean, pm, where, &dgm)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_ent, gvar, pm, where, &dgv)) return rc;
+  if (int rc = ehvi_enqueue_grad_tail(h, dmean, dvar, M, 0, dval, dgm, dgv)) return rc;
+  if (int rc = stage_out_finish(h, dval, val, M, where)) return rc;
+  if (int rc = stage_out_finish(h, dgm, gmean, pm, where)) return rc;
+  if (int rc = stage_out_finish(h, dgv, gvar, pm, where)) return rc;
+  if (int rc = finish(h)) return rc;
+  ehvi_read_tail_ms(h);
+  h->ehvi_sweep_ms = 0.0;
+  h->last_ms = h->ehvi_tail_ms;
+  h->last_launches = 1;
+  return TGP_OK;
+}
+
+// Per member, on the member's own stream: K*^T and W K* (kstar_products) and the small-predict tail into the leading handle's
+// stacked moments; on the leading stream the gradient tail; per member again the posterior's vector-Jacobian product at q = 1
+// (joint_backward) on the SAME K*^T and W K* with (gmean_j, gvar_j) as adjoints; on the leading stream the sum over the
+// members.  The streams are ordered by each handle's ev_order; the one host synchronisation is the leading stream's.
+int tgp_ehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t M, double* val, double* grad, int where) {
+  if (!hs || !hs[0]) return TGP_ERR_ARG;
+  tgp_handle h = hs[0];
+  if (M < 1 || M > JOINT_SMALL_P)
+    return fail(h, TGP_ERR_SHAPE, "M = %lld points: 1..%lld per call (chunk the points)", (long long)M, (long long)JOINT_SMALL_P);
+  if (!Xq || !val || !grad) return fail(h, TGP_ERR_ARG, "Xq / val / grad is NULL");
+  if (int rc = ehvi_check_stack(hs, P)) return rc;
+  if (int rc = set_device(h)) return rc;
+  const int d = h->d;
+  const int64_t Ppad = ((M + 63) / 64) * 64;
+  const size_t pm = (size_t)P * M, md = (size_t)M * d;
+  // every reservation first: a buffer that grows frees its old memory, which no stream may still be using
+  const double* dXq;
+  double *dval, *dgrad, *dmean, *dvar, *dgm, *dgv, *dparts;
+  if (int rc = stage_in(h, h->s_in, Xq, md, where, &dXq)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)M, where, &dval)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out2, grad, md, where, &dgrad)) return rc;
+  if (int rc = carve(h, h->s_ehvi, {{&dmean, pm}, {&dvar, pm}, {&dgm, pm}, {&dgv, pm}, {&dparts, (size_t)P * md}})) return rc;
+  JointScratch w[EHVI_MAX_P];
+  bool shared[EHVI_MAX_P];   // the member is this handle a second time: its arrays are overwritten between the two halves
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    shared[j] = false;
+    for (int i = 0; i < P; ++i) shared[j] = shared[j] || (i != j && hs[i] == t);
+    const size_t np = (size_t)t->Npad * Ppad;
+    const size_t part = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, t->dp));
+    w[j] = JointScratch{};
+    if (int rc = carve(t, t->s_grad, {{&w[j].B, np}, {&w[j].C1, np}, {&w[j].T, np}, {&w[j].Z, np}, {&w[j].part, part}})) {
+      if (t != h) h->err = t->err;
+      return rc;
+    }
+  }
+  auto member = [&](tgp_handle t, int rc) {   // errors are reported on the leading handle
+    if (rc && t != h) h->err = t->err;
+    return rc;
+  };
+  // `from`'s stream so far happens before whatever `to`'s stream is given next
+  auto order = [&](tgp_handle from, tgp_handle to) -> int {
+    if (from->stream == to->stream) return TGP_OK;
+    HIPCHK(h, hipEventRecord(from->ev_order, from->stream));
+    HIPCHK(h, hipStreamWaitEvent(to->stream, from->ev_order, 0));
+    return TGP_OK;
+  };
+  auto products = [&](int j) {
+    return kstar_products(hs[j], model_dev(hs[j]), hs[j]->d_W.as<double>(), hs[j]->Npad, dXq, M, Ppad, w[j].B, w[j].C1);
+  };
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    if (int rc = order(h, t)) return rc;   // the staged candidates
+    if (int rc = member(t, products(j))) return rc;
+    launch_predict_small_tail(t->stream, model_dev(t), M, Ppad, w[j].B, w[j].C1, w[j].part, dmean + (size_t)j * M,
+                              dvar + (size_t)j * M);
+    if (int rc = order(t, h)) return rc;
+  }
+  if (int rc = ehvi_enqueue_grad_tail(h, dmean, dvar, M, 1, dval, dgm, dgv)) return rc;
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    if (int rc = order(h, t)) return rc;   // the adjoints
+    if (shared[j])
+      if (int rc = member(t, products(j))) return rc;
+    if (int rc = member(t, joint_backward(t, w[j], dXq, M, Ppad, 1, dgm + (size_t)j * M, dgv + (size_t)j * M, dparts + (size_t)j * md)))
+      return rc;
+    if (int rc = order(t, h)) return rc;
+  }
+  launch_ehvi_sum_parts(h->stream, dparts, P, (int64_t)md, dgrad);
+  if (int rc = stage_out_finish(h, dval, val, (size_t)M, where)) return rc;
+  if (int rc = stage_out_finish(h, dgrad, grad, md, where)) return rc;
+  if (int rc = finish(h)) return rc;
+  ehvi_read_tail_ms(h);
+  h->ehvi_sweep_ms = 0.0;
+  h->last_ms = 0.0;
+  h->last_launches = P;
+  return TGP_OK;
 }
 
 int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms) {

@@ -141,7 +141,8 @@ struct tgp_handle_s {
   int ehvi_P = 0, ehvi_V = 0, ehvi_K = 0;
   int ehvi_nb[tgp::EHVI_MAX_P] = {0, 0, 0, 0};
   DevBuf d_ehvi;   // [P][V] bounds, then [K][P] packed cell words
-  DevBuf s_ehvi;   // tgp_ehvi_values / tgp_ehvi_argmax: the stack's moments, mean [P][M] then var [P][M] (16 P M bytes)
+  DevBuf s_ehvi;   // tgp_ehvi_values / tgp_ehvi_argmax: the stack's moments, mean [P][M] then var [P][M] (16 P M bytes);
+                   // tgp_ehvi_value_grad: those, their adjoints [P][M] each and the members' gradients [P][M][d]
   double ehvi_sweep_ms = 0.0, ehvi_tail_ms = 0.0;   // tgp_ehvi_last_ms
   tgp_handle rep_twin = nullptr;  // not owned: this model conditioned additionally on the pending points
   double rep_weight = 0.0;
@@ -174,6 +175,7 @@ struct tgp_handle_s {
   // (they live in a PROCESS-WIDE scratch per device, tgp_api.hip BatchScratch: every fit of every model reuses it)
   // timing of the dominant kernel
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev_order = nullptr;   // no timing: orders this handle's stream against another handle's (tgp_ehvi_value_grad)
   double last_ms = 0.0;
   int last_launches = 0;
 };

@@ -304,6 +304,15 @@ int ehvi_tile_width(int P, int V);   // candidates per workgroup: the largest po
 size_t ehvi_lds_bytes(int P, int V);
 void launch_ehvi_tail(hipStream_t s, int P, int V, const int* nb, const double* bounds, const uint32_t* cells, int K,
                       const double* mean, const double* var, int64_t M, double* out);
+// the value with the adjoints of the moments: val [M], gmean / gvar [P][M]; zero_clipped: gvar = 0 where var sits at the
+// posterior's floor.  Tile: the largest power of two <= 8 with 24 P V C <= 160 KiB
+int ehvi_grad_tile_width(int P, int V);
+size_t ehvi_grad_lds_bytes(int P, int V);
+void launch_ehvi_grad_tail(hipStream_t s, int P, int V, const int* nb, const double* bounds, const uint32_t* cells, int K,
+                           const double* mean, const double* var, int64_t M, int zero_clipped, double* val, double* gmean,
+                           double* gvar);
+// out [n] = ((part_0 + part_1) + part_2) + part_3 over the first P arrays of parts [P][n]
+void launch_ehvi_sum_parts(hipStream_t s, const double* parts, int P, int64_t n, double* out);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

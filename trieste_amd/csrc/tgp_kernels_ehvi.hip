@@ -35,7 +35,10 @@ constexpr int EHVI_LDS = 160 * 1024;
 // g: d g / d z = s cdf(z)): z^2 is taken exactly (z z = zz + ze), and the argument -z / sqrt(2) of erfc carries its rounding
 // residual r, applied to first order (d (erfc(x) / 2) / d x = -sqrt(2) pdf(z)).  Without the two corrections the relative error
 // of pdf and cdf grows like z^2 ulp, which at 36 sigma is 1e-13.
-__device__ __forceinline__ double ehvi_g(double t, double mu, double sd) {
+struct EhviEval {
+  double g, cdf, pdf;
+};
+__device__ __forceinline__ EhviEval ehvi_eval(double t, double mu, double sd) {
   t = fmax(t, -1e10);
   const double diff = t - mu;
   const double z = diff / sd;
@@ -45,7 +48,28 @@ __device__ __forceinline__ double ehvi_g(double t, double mu, double sd) {
   const double x = -z * 0.7071067811865476;
   const double r = fma(-z, 0.7071067811865476, -x) + z * 4.833646656726457e-17;  // 1 / sqrt(2) = 0.7071067811865476 - 4.83e-17
   const double cdf = fma(-1.4142135623730951 * pdf, r, 0.5 * erfc(x));
-  return fma(diff, cdf, sd * pdf);
+  return {fma(diff, cdf, sd * pdf), cdf, pdf};
+}
+__device__ __forceinline__ double ehvi_g(double t, double mu, double sd) { return ehvi_eval(t, mu, sd).g; }
+
+// The same evaluation for the derivatives d g / d m = -cdf(z), d g / d s = pdf(z), where the rounding of z does NOT cancel: z is
+// rounded three times (the difference t - mu, the square root, the quotient), each an ulp of z and so z^2 ulp of pdf and of a tail
+// cdf.  The three residuals are exact in float64 (two-sum, fma), and pdf and cdf are moved by them to first order
+// (cdf' = pdf, pdf' = -z pdf).  g is returned as ehvi_eval computes it.
+__device__ __forceinline__ EhviEval ehvi_eval_grad(double t, double mu, double var) {
+  const double sd = sqrt(var);
+  EhviEval e = ehvi_eval(t, mu, sd);
+  t = fmax(t, -1e10);
+  const double diff = t - mu, bb = diff - t;
+  const double dr = (t - (diff - bb)) + (-mu - bb);          // t - mu = diff + dr
+  const double z = diff / sd;
+  const double sr = fma(-sd, sd, var) / (2.0 * sd);          // sqrt(var) = sd + sr
+  const double dz = (dr + fma(-z, sd, diff) - z * sr) / sd;  // (t - mu) / sqrt(var) = z + dz
+  if (e.pdf > 0.0) {   // (where pdf has flushed there is nothing to move: cdf and pdf stay exactly 0 at a clipped bound)
+    e.cdf = fma(e.pdf, dz, e.cdf);
+    e.pdf = fma(-z * dz, e.pdf, e.pdf);
+  }
+  return e;
 }
 
 struct EhviDims {
@@ -138,7 +162,180 @@ void launch_ehvi_p(hipStream_t s, int V, const int* nb, const double* bounds, co
                      dims, V, cells, K, logC, out);
 }
 
+// ---- the value with the adjoints of the moments: what an L-BFGS-B iteration over EHVI asks for -------------------
+//   d EHVI / d m_j = -sum_cells (prod_{i != j} D_i) (cdf(z_u) - cdf(z_l)),   d EHVI / d s_j = sum_cells (prod_{i != j} D_i) (pdf(z_u) - pdf(z_l))
+// (d g / d m = -cdf(z), d g / d s = pdf(z): the z terms cancel because pdf' = -z pdf), D_j = max(g_j(u_j) - g_j(l_j), 0); an
+// objective of a cell whose factor the max clipped contributes no derivative.  d / d v_j = (d / d s_j) / (2 s_j).
+// Three tables g, cdf, pdf [P][V][C] (24 P V C bytes, candidate index fastest) from the SAME corrected evaluation as the value
+// kernel's; the call serves tens to 2048 points, so the tile is narrow (C <= 8: 2048 points are 256 workgroups) and a
+// function of (P, V) alone.  Per thread 1 + 2 P accumulators over its slice of the cells; the S partial sums of each quantity are
+// added in slice order by one thread, through the LDS reused after a barrier.  No atomics.
+#ifndef TGP_EHVI_GRAD_CMAX
+#define TGP_EHVI_GRAD_CMAX 8   // (build-time, for measuring: 4, 8 and 16 were compared; the bindings state 8)
+#endif
+constexpr int EHVI_GRAD_CMAX = TGP_EHVI_GRAD_CMAX;
+
+template <int P>
+__global__ __launch_bounds__(EHVI_THREADS) void ehvi_grad_tail_kernel(const double* __restrict__ mean,
+                                                                      const double* __restrict__ var, int64_t M,
+                                                                      const double* __restrict__ bounds, EhviDims dims, int V,
+                                                                      const uint32_t* __restrict__ cells, int K, int logC,
+                                                                      int zero_clipped, double* __restrict__ val,
+                                                                      double* __restrict__ gmean, double* __restrict__ gvar) {
+  extern __shared__ double G[];  // g, cdf, pdf: [P][V][C] each; afterwards [1 + 2 P][S][C] partial sums
+  const int tid = (int)threadIdx.x;
+  const int C = 1 << logC;
+  const int64_t cand0 = (int64_t)blockIdx.x << logC;
+  const int total = (P * V) << logC;
+  double* const Tc = G + total;
+  double* const Tp = Tc + total;
+
+  // phase 1: the tables (entries past an objective's bound count or past the last candidate are zero)
+  for (int e = tid; e < total; e += EHVI_THREADS) {
+    const int c = e & (C - 1), jv = e >> logC;
+    const int j = jv / V, v = jv - j * V;
+    const int64_t cand = cand0 + c;
+    EhviEval t{0.0, 0.0, 0.0};
+    if (v < dims.nb[j] && cand < M)
+      t = ehvi_eval_grad(bounds[j * V + v], mean[(int64_t)j * M + cand], var[(int64_t)j * M + cand]);
+    G[e] = t.g;
+    Tc[e] = t.cdf;
+    Tp[e] = t.pdf;
+  }
+  __syncthreads();
+
+  // phase 2: the cells of slice s for candidate lane c
+  const int c = tid & (C - 1), S = EHVI_THREADS >> logC, s = tid >> logC;
+  double acc = 0.0, am[P], as[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) am[j] = as[j] = 0.0;
+  if (s < K) {
+    uint32_t w[P], wn[P] = {};
+#pragma unroll
+    for (int j = 0; j < P; ++j) w[j] = cells[(size_t)s * P + j];
+    for (int k = s; k < K; k += S) {
+      const int kn = k + S;
+      if (kn < K) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) wn[j] = cells[(size_t)kn * P + j];
+      }
+      double del[P], dc[P], dp[P];
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        const int il = (((j * V) + (int)(w[j] & 0xffffu)) << logC) + c;
+        const int iu = (((j * V) + (int)(w[j] >> 16)) << logC) + c;
+        const double d = G[iu] - G[il];
+        const bool pos = d > 0.0;   // (the derivative of the function as computed: a clipped factor has none)
+        del[j] = pos ? d : 0.0;
+        dc[j] = pos ? Tc[iu] - Tc[il] : 0.0;
+        dp[j] = pos ? Tp[iu] - Tp[il] : 0.0;
+      }
+      double f = 1.0;
+#pragma unroll
+      for (int j = 0; j < P; ++j) f *= del[j];
+      acc += f;
+      double loo[P];   // the products that leave one objective out, without a division
+      if constexpr (P == 2) {
+        loo[0] = del[1];
+        loo[1] = del[0];
+      } else if constexpr (P == 3) {
+        loo[0] = del[1] * del[2];
+        loo[1] = del[0] * del[2];
+        loo[2] = del[0] * del[1];
+      } else {
+        const double a = del[0] * del[1], b = del[2] * del[3];
+        loo[0] = del[1] * b;
+        loo[1] = del[0] * b;
+        loo[2] = a * del[3];
+        loo[3] = a * del[2];
+      }
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        am[j] = fma(loo[j], dc[j], am[j]);
+        as[j] = fma(loo[j], dp[j], as[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < P; ++j) w[j] = wn[j];
+    }
+  }
+  __syncthreads();
+  G[tid] = acc;  // [quantity][s][c]
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    G[(1 + j) * EHVI_THREADS + tid] = am[j];
+    G[(1 + P + j) * EHVI_THREADS + tid] = as[j];
+  }
+  __syncthreads();
+  if (tid < ((1 + 2 * P) << logC)) {
+    const int q = tid >> logC, cc = tid & (C - 1);
+    const int64_t cand = cand0 + cc;
+    if (cand < M) {
+      const double* const R = G + q * EHVI_THREADS + cc;
+      double sum = 0.0;
+      for (int t = 0; t < S; ++t) sum += R[t << logC];
+      if (q == 0) {
+        val[cand] = sum;
+      } else if (q <= P) {
+        gmean[(int64_t)(q - 1) * M + cand] = 0.0 - sum;
+      } else {
+        const double v = var[(int64_t)(q - 1 - P) * M + cand];
+        // (zero_clipped: a variance at the posterior's floor was clipped there, and the clip's adjoint is zero)
+        gvar[(int64_t)(q - 1 - P) * M + cand] = zero_clipped && !(v > VAR_FLOOR) ? 0.0 : sum / (2.0 * sqrt(v));
+      }
+    }
+  }
+}
+
+template <int P>
+void launch_ehvi_grad_p(hipStream_t s, int V, const int* nb, const double* bounds, const uint32_t* cells, int K,
+                        const double* mean, const double* var, int64_t M, int zero_clipped, double* val, double* gmean,
+                        double* gvar) {
+  (void)hipFuncSetAttribute((const void*)ehvi_grad_tail_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, EHVI_LDS);
+  const int C = ehvi_grad_tile_width(P, V);
+  int logC = 0;
+  while ((1 << logC) < C) ++logC;
+  EhviDims dims{};
+  for (int j = 0; j < P; ++j) dims.nb[j] = nb[j];
+  const int64_t grid = (M + C - 1) / C;
+  hipLaunchKernelGGL(ehvi_grad_tail_kernel<P>, dim3((unsigned)grid), dim3(EHVI_THREADS), ehvi_grad_lds_bytes(P, V), s, mean, var, M,
+                     bounds, dims, V, cells, K, logC, zero_clipped, val, gmean, gvar);
+}
+
+// out [n] = ((part_0 + part_1) + part_2) + part_3 over the first P of the arrays part_j = parts + j n: one fixed association
+__global__ void ehvi_sum_parts_kernel(const double* __restrict__ parts, int P, int64_t n, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double sum = parts[i];
+  for (int j = 1; j < P; ++j) sum += parts[(int64_t)j * n + i];
+  out[i] = sum;
+}
+
 }  // namespace
+
+int ehvi_grad_tile_width(int P, int V) {
+  int C = EHVI_GRAD_CMAX;
+  while (C > 1 && (size_t)24 * P * V * C > (size_t)EHVI_LDS) C >>= 1;
+  return C;
+}
+
+size_t ehvi_grad_lds_bytes(int P, int V) {
+  const size_t table = (size_t)24 * P * V * ehvi_grad_tile_width(P, V), sums = (size_t)8 * EHVI_THREADS * (1 + 2 * P);
+  return table > sums ? table : sums;
+}
+
+void launch_ehvi_grad_tail(hipStream_t s, int P, int V, const int* nb, const double* bounds, const uint32_t* cells, int K,
+                           const double* mean, const double* var, int64_t M, int zero_clipped, double* val, double* gmean,
+                           double* gvar) {
+  if (M <= 0) return;
+  if (P == 2) launch_ehvi_grad_p<2>(s, V, nb, bounds, cells, K, mean, var, M, zero_clipped, val, gmean, gvar);
+  else if (P == 3) launch_ehvi_grad_p<3>(s, V, nb, bounds, cells, K, mean, var, M, zero_clipped, val, gmean, gvar);
+  else launch_ehvi_grad_p<4>(s, V, nb, bounds, cells, K, mean, var, M, zero_clipped, val, gmean, gvar);
+}
+
+void launch_ehvi_sum_parts(hipStream_t s, const double* parts, int P, int64_t n, double* out) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ehvi_sum_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, parts, P, n, out);
+}
 
 int ehvi_tile_width(int P, int V) {
   int C = 64;

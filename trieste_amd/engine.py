@@ -931,6 +931,48 @@ def ehvi_argmax(engines, Xq, index_base: int = 0):
     return bv.value, bi.value, bx
 
 
+EHVI_GRAD_MAX_POINTS = 2048  # points per tgp_ehvi_value_grad call (callers chunk)
+
+
+def ehvi_grad_tile_width(P: int, V: int) -> int:
+    """Candidates per workgroup of the EHVI gradient kernel: the largest power of two <= 8 whose three tables of
+    24 P V C bytes fit 160 KiB of LDS.  A function of (P, V) alone; 2 at P = 4, V = 512."""
+    C = 8
+    while C > 1 and 24 * P * V * C > 160 * 1024:
+        C //= 2
+    return C
+
+
+def ehvi_moments_grad(engine, mean, var):
+    """The EHVI tail with the adjoints of the moments on caller-supplied moments: mean, var [P, M] objective-major ->
+    (value [M], gmean [P, M], gvar [P, M]) (tgp_ehvi_moments_grad).  Needs a partition on the engine and no data."""
+    m, v = _Arg(mean), _Arg(var)
+    if len(m.shape) != 2 or m.shape != v.shape:
+        raise ValueError(f"mean and var must both be [P, M], got {m.shape} and {v.shape}")
+    if m.where != v.where:
+        raise ValueError("mean and var must live in the same place (both host or both device)")
+    val, pv = GPEngine._out(m, (m.shape[1],))
+    gm, pgm = GPEngine._out(m, m.shape)
+    gv, pgv = GPEngine._out(m, m.shape)
+    engine._chk(engine._lib.tgp_ehvi_moments_grad(engine._h, m.ptr, v.ptr, int(m.shape[1]), pv, pgm, pgv, m.where))
+    return val, gm, gv
+
+
+def ehvi_value_grad(engines, Xq):
+    """engines: one :class:`GPEngine` per objective (the first carries the partition); Xq [M, d], 1 <= M <= 2048 ->
+    (EHVI [M], its gradient [M, d]) in one device call: every engine's small-product posterior, the gradient tail, every
+    engine's vector-Jacobian product and their sum (tgp_ehvi_value_grad)."""
+    engines, hs = _handles(engines)
+    a = _Arg(Xq)
+    if len(a.shape) != 2 or a.shape[1] != engines[0].d:
+        raise ValueError(f"Xq must be [M, {engines[0].d}], got shape {tuple(a.shape)}")
+    M = int(a.shape[0])
+    val, pv = GPEngine._out(a, (M,))
+    grad, pg = GPEngine._out(a, (M, engines[0].d))
+    engines[0]._chk(engines[0]._lib.tgp_ehvi_value_grad(hs, len(engines), a.ptr, M, pv, pg, a.where))
+    return val, grad
+
+
 def ehvi_last_ms(engine):
     """(summed time of the posterior sweeps, time of the tail kernel) of the engine's most recent EHVI call, in ms."""
     s, t = C.c_double(), C.c_double()
