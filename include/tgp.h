@@ -354,6 +354,44 @@ int tgp_ehvi_moments_grad(tgp_handle h, const double* mean, const double* var, i
 int tgp_ehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t M, double* val, double* grad, int where);
 int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms);
 
+/* ---- batch Monte-Carlo expected hypervolume improvement ---------------------------------- */
+/* == batch_ehvi.__call__ (acquisition/function/multi_objective.py:366-410) behind BatchReparametrizationSampler.sample over a
+ * stack of P independent exact GPRs (minimisation), for G batches of q points, on the cells that tgp_set_ehvi_partition keeps
+ * on the leading handle:
+ *     L_j      = chol(cov[j,g] + jitter I)                      j = 0..P-1, each q x q
+ *     y[s,i,j] = mean[j,g,i] + sum_m L_j[i,m] eps[j,m,s]
+ *     out[g]   = (1/S) sum_s sum_k sum_{J != {}} (-1)^(|J|+1) prod_j max(ub[k,j] - max(lb[k,j], max_{i in J} y[s,i,j]), 0)
+ * (inclusion-exclusion over the 2^q - 1 subsets J of the batch: the hypervolume improvement of the union of the q sampled
+ * points).  A lower bound below -1e10 is taken as -1e10, as the EHVI kernel takes it.  Value only.
+ * Layouts: mean [P,G,q] and cov [P,G,q,q] OBJECTIVE-MAJOR; eps [P,q,S] (the stack sampler's [L,B,S]: every objective has its
+ * own draws); Xq [G,q,d]; out [G]; host or device alike.
+ * Limits: 2 <= P <= 4 (the partition's), 1 <= q <= TGP_QEHVI_MAX_Q, S >= 1, any G >= 0; else TGP_ERR_SHAPE (q, G) or
+ * TGP_ERR_ARG (S, eps, jitter < 0).  One workgroup per batch keeps the samples in LDS, 8 P q bytes each, C samples at a time:
+ *     C = min(512, the largest multiple of 64 with 8 P q C <= 32 KiB)      (512 up to P q = 8, 128 at P = 4, q = 8)
+ * a function of (P, q) alone; S has no upper limit.
+ * float64 throughout, no atomics on a value.  The subsets are walked depth first in lexicographic order and the terms added
+ * in that order per (sample, cell); cells, samples, the four cell slices and the 64 lanes are added in fixed orders
+ * (DESIGN.md 4.6): the summation order is a function of (P, q, S, K) alone.  A batch's value depends on its own moments, eps,
+ * jitter and the partition only -- not on G, its position in the call, its neighbours or the handle's history -- and
+ * identical calls return identical bits.
+ * TGP_ERR_NOT_PD: a non-positive pivot in any of a batch's P factorisations, naming the group by its index in the call,
+ * reported as tgp_batch_ei reports it above: the groups are walked in chunks of at most 2^28 / (8 P q (q + 1)), so that
+ * the chunk's moments stay within 256 MiB of scratch, and the first chunk that holds such a group ends the call.
+ *   tgp_qehvi_moments: the tail alone on caller-supplied moments AS THE MODEL RETURNS THEM (the entry adds the jitter); P is
+ *     the partition's; needs no data on the handle.  TGP_ERR_STATE without a partition.
+ *   tgp_qehvi_values: handle checks exactly those of tgp_ehvi_values.  Xq is staged once; per chunk every handle's
+ *     (mean, cov) comes from tgp_predict_joint ITSELF on that handle (the small-product path up to G q = 2048 points of the
+ *     chunk, the joint kernel above), written objective-major into scratch of the leading handle, then the tail on the leading
+ *     handle's stream.  The handles may use different streams (tgp_predict_joint synchronises its own); the tail and the
+ *     copy back end in one host synchronisation per chunk.
+ * tgp_ehvi_last_ms reports the two calls as the five above: the summed time of the posterior kernels (0 for
+ * tgp_qehvi_moments) and the summed time of the tail kernel over the chunks. */
+#define TGP_QEHVI_MAX_Q 8
+int tgp_qehvi_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
+                      double jitter, double* out, int where);
+int tgp_qehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t G, int q, const double* eps, int S, double jitter,
+                     double* out, int where);
+
 /* == BatchReparametrizationSampler.sample (sampler.py:208-287) itself: out [G,S,q] = mean +
  * (chol(cov + jitter*I) eps)^T for Xq [G,q,d], eps [q,S].  q <= 64. */
 int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S,

@@ -70,6 +70,8 @@ SIGNATURES = {
     "tgp_ehvi_moments_grad": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int]),
     "tgp_ehvi_value_grad": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_int]),
     "tgp_ehvi_last_ms": (C.c_int, [_vp, _dp, _dp]),
+    "tgp_qehvi_moments": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int]),
+    "tgp_qehvi_values": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int]),
     "tgp_reparam_samples": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int]),
     "tgp_traj_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_create_rff": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
@@ -162,6 +164,7 @@ PRECISIONS = {"f64": 0, "i8x4": 1, "i8x5": 2, "auto": 3}
 MAX_D = 1024      # input dimensions tgp_create accepts (include/tgp.h)
 NARROW_MAX_D = 32  # above it: float64 sweeps only (no int8 rungs), no trajectories
 EHVI_MAX_P, EHVI_MAX_BOUNDS, EHVI_MAX_CELLS = 4, 512, 1 << 21  # limits of the tgp_ehvi_* calls (include/tgp.h)
+QEHVI_MAX_Q = 8  # points per batch of the tgp_qehvi_* calls (TGP_QEHVI_MAX_Q)
 
 
 def check(lib, handle, rc, group=False):

@@ -28,16 +28,11 @@ def _stack_engines(model, who: str):
     return engines
 
 
-class expected_hv_improvement(AcquisitionFunctionClass):
-    """EHVI of a single point under independent Gaussian marginals, for minimisation, over the cells ``partition_bounds``
-    = (lower [K, P], upper [K, P]) of the non-dominated region.  The bound values are turned into per-objective tables of
-    distinct values and per-cell indices here (exact float64 values) and live on the leading engine of the stack."""
-
-    def __init__(self, model, partition_bounds):
-        self._model = model
-        engines = _stack_engines(model, type(self).__name__)
-        self._engine = engines[0]
-        self.update(partition_bounds)
+class _PartitionOwner:
+    """What the function objects over a stack share: their cells as the engine's tables, and the ownership token under which
+    they sit on the stack's leading engine.  The partition is engine state: another function object over the same stack (an
+    EHVI and a batch EHVI function, say), or a re-attached engine of a copied model, may have replaced it, so every call
+    goes through :meth:`_engines`, which installs this object's cells unless the engine still carries its token."""
 
     def update(self, partition_bounds) -> None:
         """New cells (the front moved)."""
@@ -52,14 +47,25 @@ class expected_hv_improvement(AcquisitionFunctionClass):
         self._token = object()   # identifies (this function, this partition); never recurs while the engine holds it
 
     def _engines(self):
-        """The stack's engines with this function's partition installed on the first (it is engine state: another function
-        object over the same stack, or a re-attached engine of a copied model, may have replaced it)."""
+        """The stack's engines with this function's partition installed on the first."""
         engines = _stack_engines(self._model, type(self).__name__)
         self._engine = lead = engines[0]
         if getattr(lead, "_ehvi_owner", None) is not self._token:
             _engine_mod.ehvi_set_partition_tables(lead, *self._tables)   # (clears the engine's owner mark)
             lead._ehvi_owner = self._token
         return engines
+
+
+class expected_hv_improvement(_PartitionOwner, AcquisitionFunctionClass):
+    """EHVI of a single point under independent Gaussian marginals, for minimisation, over the cells ``partition_bounds``
+    = (lower [K, P], upper [K, P]) of the non-dominated region.  The bound values are turned into per-objective tables of
+    distinct values and per-cell indices here (exact float64 values) and live on the leading engine of the stack."""
+
+    def __init__(self, model, partition_bounds):
+        self._model = model
+        engines = _stack_engines(model, type(self).__name__)
+        self._engine = engines[0]
+        self.update(partition_bounds)
 
     def _points(self, x):
         if not _is_torch(x):

@@ -3467,6 +3467,126 @@ int tgp_ehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t M
   return TGP_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// ---- batch Monte-Carlo EHVI (tgp_kernels_qehvi.hip) ---------------------------------------------------------------
+static_assert(QEHVI_MAX_Q == TGP_QEHVI_MAX_Q, "the header publishes the kernel's bound");
+constexpr const char* QEHVI_NOT_PD ="qEHVI: a covariance of group %lld is not positive definite (cov + jitter*I)";
+
+int qehvi_check(tgp_handle h, int64_t G, int q, const double* eps, int S, double jitter) {
+  if (q < 1 || q > QEHVI_MAX_Q) return fail(h, TGP_ERR_SHAPE, "qEHVI: q must be in 1..%d, got %d", QEHVI_MAX_Q, q);
+  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
+  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  if (G < 0) return fail(h, TGP_ERR_SHAPE, "G must be >= 0");
+  return TGP_OK;
+}
+
+// groups per chunk: the chunk's moments, 8 P (q + q^2) bytes per group, stay within 256 MiB
+int64_t qehvi_group_chunk(int P, int q) {
+  return std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)8 * P * q * (q + 1)));
+}
+
+// the tail on device-resident moments of `gc` groups (objective stride `gstride` groups), bracketed by the handle's events
+int qehvi_enqueue_tail(tgp_handle h, const double* dmean, const double* dcov, int64_t gc, int64_t gstride, int q,
+                       const double* deps, int S, double jitter, double* dout) {
+  const double* db = h->d_ehvi.as<double>();
+  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_qehvi_tail(h->stream, h->ehvi_P, h->ehvi_V, db, dc, h->ehvi_K, dmean, dcov, gc, gstride, q, deps, S, jitter, dout,
+                    h->d_info.as<int>());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return TGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tgp_qehvi_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
+                      double jitter, double* out, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = ehvi_need_partition(h)) return rc;
+  if (int rc = qehvi_check(h, G, q, eps, S, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!mean || !cov || !out) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  const int P = h->ehvi_P;
+  const int64_t qq = (int64_t)q * q;
+  const double* deps;
+  if (int rc = stage_in(h, h->s_in2, eps, (size_t)P * q * S, where, &deps)) return rc;
+  const int rc = for_group_chunks(h, G, qehvi_group_chunk(P, q), true, QEHVI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    const double *dmean = mean + g0 * q, *dcov = cov + g0 * qq;
+    int64_t gstride = G;
+    double* dout;
+    if (where != TGP_DEVICE) {   // objective j's groups of this chunk behind each other: [P][gc]
+      HIPCHK(h, h->s_out1.reserve((size_t)P * gc * q * sizeof(double)));
+      HIPCHK(h, h->s_out2.reserve((size_t)P * gc * qq * sizeof(double)));
+      for (int j = 0; j < P; ++j) {
+        HIPCHK(h, hipMemcpyAsync(h->s_out1.as<double>() + (size_t)j * gc * q, mean + ((int64_t)j * G + g0) * q,
+                                 (size_t)gc * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->s_out2.as<double>() + (size_t)j * gc * qq, cov + ((int64_t)j * G + g0) * qq,
+                                 (size_t)gc * qq * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      }
+      dmean = h->s_out1.as<double>();
+      dcov = h->s_out2.as<double>();
+      gstride = gc;
+    }
+    if (int rb = stage_out_prepare(h, h->s_out3, out + g0, (size_t)gc, where, &dout)) return rb;
+    if (int rb = qehvi_enqueue_tail(h, dmean, dcov, gc, gstride, q, deps, S, jitter, dout)) return rb;
+    return stage_out_finish(h, dout, out + g0, (size_t)gc, where);
+  });
+  h->ehvi_sweep_ms = 0.0;
+  h->ehvi_tail_ms = h->last_ms;
+  return rc;
+}
+
+int tgp_qehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t G, int q, const double* eps, int S, double jitter,
+                     double* out, int where) {
+  if (!hs || !hs[0]) return TGP_ERR_ARG;
+  tgp_handle h = hs[0];
+  if (int rc = ehvi_check_stack(hs, P)) return rc;
+  if (int rc = qehvi_check(h, G, q, eps, S, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!Xq || !out) return fail(h, TGP_ERR_ARG, "Xq / out is NULL");
+  if (int rc = set_device(h)) return rc;
+  const int d = h->d;
+  const int64_t qq = (int64_t)q * q;
+  const double *dXq, *deps;
+  if (int rc = stage_in(h, h->s_in, Xq, (size_t)G * q * d, where, &dXq)) return rc;
+  if (int rc = stage_in(h, h->s_in2, eps, (size_t)P * q * S, where, &deps)) return rc;
+  if (where != TGP_DEVICE)
+    if (int rc = sync(h)) return rc;  // the other members read the staged points from their own streams
+  const int64_t chunk = qehvi_group_chunk(P, q);
+  double *dmean, *dcov;
+  const size_t gmax = (size_t)std::min(chunk, G);
+  if (int rc = carve(h, h->s_ehvi, {{&dmean, (size_t)P * gmax * q}, {&dcov, (size_t)P * gmax * qq}})) return rc;
+  double sweep_ms = 0.0;
+  const int rc = for_group_chunks(h, G, chunk, true, QEHVI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    for (int j = 0; j < P; ++j) {
+      // (tgp_predict_joint drains the member's stream before it returns: the tail below may run on the leading stream)
+      if (int rb = tgp_predict_joint(hs[j], dXq + g0 * q * d, gc, q, dmean + (size_t)j * gc * q, dcov + (size_t)j * gc * qq,
+                                     TGP_DEVICE)) {
+        if (hs[j] != h) h->err = hs[j]->err;
+        return rb;
+      }
+      float ms = 0.f;   // both posterior paths leave the member's two events around their kernels
+      if (hipEventElapsedTime(&ms, hs[j]->ev0, hs[j]->ev1) == hipSuccess) sweep_ms += ms;
+      (void)hipGetLastError();
+    }
+    if (int rb = set_device(h)) return rb;
+    double* dout;
+    if (int rb = stage_out_prepare(h, h->s_out3, out + g0, (size_t)gc, where, &dout)) return rb;
+    if (int rb = qehvi_enqueue_tail(h, dmean, dcov, gc, gc, q, deps, S, jitter, dout)) return rb;
+    return stage_out_finish(h, dout, out + g0, (size_t)gc, where);
+  });
+  h->ehvi_sweep_ms = sweep_ms;
+  h->ehvi_tail_ms = h->last_ms;
+  h->last_ms = sweep_ms;
+  return rc;
+}
+
 int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms) {
   if (!h) return TGP_ERR_ARG;
   if (sweeps_ms) *sweeps_ms = h->ehvi_sweep_ms;

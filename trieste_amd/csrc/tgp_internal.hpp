@@ -313,6 +313,17 @@ void launch_ehvi_grad_tail(hipStream_t s, int P, int V, const int* nb, const dou
                            double* gvar);
 // out [n] = ((part_0 + part_1) + part_2) + part_3 over the first P arrays of parts [P][n]
 void launch_ehvi_sum_parts(hipStream_t s, const double* parts, int P, int64_t n, double* out);
+// batch Monte-Carlo EHVI on given joint moments (tgp_kernels_qehvi.hip): mean [P][gstride][q], cov [P][gstride][q][q] (the
+// launch takes the first G groups of every objective), eps [P][q][S], bounds / cells as above, out [G]; info: the 1-based group
+// of a non-positive pivot (first report wins).  One workgroup per group, QEHVI_SLICES waves = cell slices, lane = sample.
+constexpr int QEHVI_MAX_Q = 8, QEHVI_SLICES = 4;
+constexpr int QEHVI_SAMPLE_LDS = 32 * 1024, QEHVI_MAX_CHUNK = 512;
+// samples per LDS pass: the largest multiple of 64 with 8 P q C <= 32 KiB, at most 512 (128 at P = 4, q = 8)
+int qehvi_sample_chunk(int P, int q);
+size_t qehvi_lds_bytes(int P, int q, int S);
+void launch_qehvi_tail(hipStream_t s, int P, int V, const double* bounds, const uint32_t* cells, int K, const double* mean,
+                       const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
+                       double* out, int* info);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

@@ -978,3 +978,62 @@ def ehvi_last_ms(engine):
     s, t = C.c_double(), C.c_double()
     engine._chk(engine._lib.tgp_ehvi_last_ms(engine._h, C.byref(s), C.byref(t)))
     return s.value, t.value
+
+
+# ---- batch Monte-Carlo expected hypervolume improvement (tgp_qehvi_*; include/tgp.h) -----------------------------------
+QEHVI_MAX_Q = _lib.QEHVI_MAX_Q
+QEHVI_SLICES = 4  # cell slices of the qEHVI kernel (one wave each): slice w takes cells w, w + 4, ...
+
+
+def qehvi_sample_chunk(P: int, q: int) -> int:
+    """Samples the qEHVI kernel keeps in LDS at a time: the largest multiple of 64 with 8 P q C <= 32 KiB, at most 512.  A
+    function of (P, q) alone; 128 at P = 4, q = 8."""
+    return min(512, (32 * 1024 // (8 * P * q)) // 64 * 64)
+
+
+def qehvi_sum_roundings(P: int, q: int, S: int, K: int) -> int:
+    """The rounding count of the qEHVI kernel's documented summation: P + 1 per product, the 2^q - 1 terms of
+    a (sample, cell), a lane's cells-of-its-slice x samples, the 3 additions over the slices, the 6 of the butterfly over the
+    lanes and the division by S."""
+    return (P + 1) + (2 ** q - 1) + -(-K // QEHVI_SLICES) * -(-S // 64) + 3 + 6 + 1
+
+
+def _qehvi_eps(P: int, q: int, eps, where):
+    e = _Arg(eps)
+    if len(e.shape) != 3 or e.shape[0] != P or e.shape[1] != q:
+        raise ValueError(f"eps must be [P={P}, q={q}, S], got {e.shape}")
+    if e.where != where:
+        raise ValueError("the moments or points and eps must live in the same place (both host or both device)")
+    return e
+
+
+def qehvi_moments(engine, mean, cov, eps, jitter: float = 1e-6):
+    """The qEHVI tail on caller-supplied joint moments as the models return them: mean [P, ..., q], cov [P, ..., q, q]
+    objective-major, eps [P, q, S] -> [...] (tgp_qehvi_moments).  Needs a partition on the engine and no data."""
+    m, c = _Arg(mean), _Arg(cov)
+    if len(m.shape) < 2 or c.shape != m.shape + (m.shape[-1],):
+        raise ValueError(f"mean must be [P, ..., q] and cov [P, ..., q, q], got {m.shape} and {c.shape}")
+    if m.where != c.where:
+        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    P, lead, q = m.shape[0], m.shape[1:-1], m.shape[-1]
+    G = int(np.prod(lead)) if lead else 1
+    e = _qehvi_eps(P, q, eps, m.where)
+    out, po = GPEngine._out(m, lead)
+    engine._chk(engine._lib.tgp_qehvi_moments(engine._h, m.ptr, c.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter), po, m.where))
+    return out
+
+
+def qehvi_values(engines, Xq, eps, jitter: float = 1e-6):
+    """engines: one :class:`GPEngine` per objective (the first carries the partition); Xq [..., q, d], eps [P, q, S] ->
+    qEHVI [...]: every engine's ``predict_joint`` and the tail in one device call (tgp_qehvi_values)."""
+    engines, hs = _handles(engines)
+    a = _Arg(Xq)
+    if len(a.shape) < 2 or a.shape[-1] != engines[0].d:
+        raise ValueError(f"batch query points must be [..., q, {engines[0].d}], got {a.shape}")
+    lead, q = a.shape[:-2], a.shape[-2]
+    G = int(np.prod(lead)) if lead else 1
+    e = _qehvi_eps(len(engines), q, eps, a.where)
+    out, po = GPEngine._out(a, lead)
+    engines[0]._chk(engines[0]._lib.tgp_qehvi_values(hs, len(engines), a.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter), po,
+                                                     a.where))
+    return out

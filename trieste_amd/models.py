@@ -752,6 +752,24 @@ class ModelStack:
         """[..., N, D] -> [..., S, N, number of models]."""
         return np.concatenate([np.asarray(model.sample(query_points, num_samples)) for model in self._models], axis=-1)
 
+    def predict_joint(self, query_points):
+        """[..., B, D] -> (mean [..., B, number of models], cov [..., number of models, B, B]): the members' joint
+        posteriors, means concatenated on the event axis and covariances on axis -3 (interfaces.py:489-499)."""
+        means, covs = zip(*[model.predict_joint(query_points) for model in self._models])
+        return np.concatenate([np.asarray(m) for m in means], axis=-1), \
+            np.concatenate([np.asarray(c) for c in covs], axis=-3)
+
+    def reparam_sampler(self, num_samples: int):
+        """A reparametrization sampler of ``num_samples`` samples across all the models of the stack: the members'
+        sampler type over the stack, if they all build the same type (interfaces.py:453-479)."""
+        samplers = [model.reparam_sampler(num_samples) for model in self._models]
+        unique_sampler_types = set(type(sampler) for sampler in samplers)
+        if len(unique_sampler_types) == 1:
+            return type(samplers[0])(num_samples, self)
+        raise NotImplementedError(
+            "Reparameterization sampling is only currently supported for model stacks built from models that use the "
+            f"same reparameterization sampler, however, received samplers of types {unique_sampler_types}.")
+
     def log(self, dataset: Optional[Dataset] = None) -> None:
         for model in self._models:
             model.log(dataset)
@@ -773,3 +791,16 @@ class TrainableModelStack(ModelStack):
 
     def optimize(self, dataset: Dataset):
         return [model.optimize(data) for model, data in zip(self._models, self._split(dataset))]
+
+
+# the reference's names for stacks with these capabilities (interfaces.py:445-499, 537-545): here every stack has them
+class PredictJointModelStack(ModelStack):
+    """A :class:`ModelStack` under the reference's name for stacks that delegate ``predict_joint``."""
+
+
+class HasReparamSamplerModelStack(ModelStack):
+    """A :class:`ModelStack` under the reference's name for stacks that provide ``reparam_sampler``."""
+
+
+class TrainablePredictJointReparamModelStack(TrainableModelStack, PredictJointModelStack, HasReparamSamplerModelStack):
+    """A :class:`TrainableModelStack` under the reference's name for trainable stacks with both."""

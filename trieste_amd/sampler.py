@@ -60,7 +60,7 @@ class BatchReparametrizationSampler:
         self._sample_size = sample_size
         self._model = model
         self._rng = make_rng(seed)
-        self._eps: Optional[np.ndarray] = None  # [B, S]
+        self._eps: Optional[np.ndarray] = None  # [B, S]; over a stack of L models [L, B, S]
         self._initialized = False
 
     def __repr__(self) -> str:
@@ -74,33 +74,46 @@ class BatchReparametrizationSampler:
         """Resample eps on the next call (reference ReparametrizationSampler.reset_sampler)."""
         self._initialized = False
 
+    def _members(self):
+        """The models of a stack (``ModelStack._models``), or None over a single model."""
+        return getattr(self._model, "_models", None)
+
     def eps(self, batch_size: int) -> np.ndarray:
-        """The fixed draws [B, S] for this batch size (drawn on first use / after a reset)."""
+        """The fixed draws for this batch size (drawn on first use / after a reset): [B, S] over a single model, [L, B, S]
+        over a stack of L models, every model with draws of its own (reference sampler.py:239-258)."""
         if batch_size <= 0:
             raise ValueError(f"batch size must be positive, got {batch_size}")
+        members = self._members()
+        L = 1 if members is None else len(members)
         if not self._initialized or self._eps is None:
-            if self._qmc:  # Sobol points [S, B] -> [B, S] (sampler.py:241-256)
+            if self._qmc:  # Sobol points [S * L, B] -> [L, S, B] -> [L, B, S] (sampler.py:241-256)
                 skip = _QmcSkip.skip if self._qmc_skip else 0
                 if self._qmc_skip:
                     _QmcSkip.skip += self._sample_size
-                self._eps = np.ascontiguousarray(qmc_normal_samples(self._sample_size, batch_size, skip).T)
+                pts = qmc_normal_samples(self._sample_size * L, batch_size, skip)
+                eps = np.ascontiguousarray(pts.reshape(L, self._sample_size, batch_size).transpose(0, 2, 1))
             else:
-                self._eps = self._rng.standard_normal((batch_size, self._sample_size))
+                eps = self._rng.standard_normal((L, batch_size, self._sample_size))
+            self._eps = eps[0] if members is None else eps
             self._initialized = True
-        elif self._eps.shape[0] != batch_size:
+        elif self._eps.shape[-2] != batch_size:
             raise ValueError(f"{type(self).__name__} requires a fixed batch size. Got batch size {batch_size} "
-                             f"but previous batch size was {self._eps.shape[0]}.")
+                             f"but previous batch size was {self._eps.shape[-2]}.")
         return self._eps
 
     def sample(self, at, *, jitter: float = JITTER):
-        """at [..., B, D] -> samples [..., S, B, 1]; identical across calls for the same ``at``."""
+        """at [..., B, D] -> samples [..., S, B, L] (L = 1 over a single model); identical across calls for the same
+        ``at``.  Over a stack every member engine draws with its own slice of eps."""
         at = np.asarray(at, dtype=np.float64)
         if at.ndim < 2:
             raise ValueError(f"at must have rank >= 2, got shape {at.shape}")
         if jitter < 0:
             raise ValueError(f"jitter must be non-negative, got {jitter}")
         eps = self.eps(at.shape[-2])
-        return self._model.engine.reparam_samples(at, eps, jitter)[..., None]
+        members = self._members()
+        if members is None:
+            return self._model.engine.reparam_samples(at, eps, jitter)[..., None]
+        return np.stack([np.asarray(m.engine.reparam_samples(at, eps[j], jitter)) for j, m in enumerate(members)], axis=-1)
 
 
 class IndependentReparametrizationSampler:
