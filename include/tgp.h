@@ -362,7 +362,7 @@ int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms);
  *     y[s,i,j] = mean[j,g,i] + sum_m L_j[i,m] eps[j,m,s]
  *     out[g]   = (1/S) sum_s sum_k sum_{J != {}} (-1)^(|J|+1) prod_j max(ub[k,j] - max(lb[k,j], max_{i in J} y[s,i,j]), 0)
  * (inclusion-exclusion over the 2^q - 1 subsets J of the batch: the hypervolume improvement of the union of the q sampled
- * points).  A lower bound below -1e10 is taken as -1e10, as the EHVI kernel takes it.  Value only.
+ * points).  A lower bound below -1e10 is taken as -1e10, as the EHVI kernel takes it.
  * Layouts: mean [P,G,q] and cov [P,G,q,q] OBJECTIVE-MAJOR; eps [P,q,S] (the stack sampler's [L,B,S]: every objective has its
  * own draws); Xq [G,q,d]; out [G]; host or device alike.
  * Limits: 2 <= P <= 4 (the partition's), 1 <= q <= TGP_QEHVI_MAX_Q, S >= 1, any G >= 0; else TGP_ERR_SHAPE (q, G) or
@@ -385,12 +385,45 @@ int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms);
  *     handle's stream.  The handles may use different streams (tgp_predict_joint synchronises its own); the tail and the
  *     copy back end in one host synchronisation per chunk.
  * tgp_ehvi_last_ms reports the two calls as the five above: the summed time of the posterior kernels (0 for
- * tgp_qehvi_moments) and the summed time of the tail kernel over the chunks. */
+ * tgp_qehvi_moments) and the summed time of the tail kernel over the chunks.
+ *
+ * The gradient (what tfp.math.value_and_gradient takes through predict_joint, the Cholesky factors and the reparametrised
+ * samples when the reference hands batch_ehvi to batchify_joint(generate_continuous_optimizer)).  With
+ * a[i][j] = ub[k,j] - clamp(y[s,i,j], lb[k,j], ub[k,j]) the term of (cell k, subset J) is sign(J) prod_j n_J[j],
+ * n_J[j] = min_{i in J} a[i][j], and
+ *     d term / d y[s,i*,j] = -sign(J) prod_{j' != j} n_J[j']
+ * where i* is the point of J that attains the minimum in objective j.  Two conventions fix the ties (sets of measure zero):
+ * the comparison is strict, so the first point of J in walk order (the smallest index) wins; and the derivative is non-zero
+ * only where lb < y < ub strictly -- a sample clamped at a bound contributes nothing.  Then
+ *     ybar[s,i,j] = sum over cells and subsets,   gmean[j,g,i] = (1/S) sum_s ybar[s,i,j],
+ *     Lbar_j = (1/S) tril(sum_s ybar[s,.,j] eps[j,.,s]^T),   gcov[j,g] = L_j^-T sym(Phi(L_j^T Lbar_j)) L_j^-1
+ * (Phi keeps the lower triangle and halves the diagonal): gcov is the SYMMETRIC adjoint that tgp_joint_vjp takes.
+ * val is the value of tgp_qehvi_moments / tgp_qehvi_values BIT FOR BIT (same factorisation, same sample chain, same
+ * summation order).  The kernel keeps, besides the samples, one adjoint slot per sample and cell slice in LDS (up to 160 KiB):
+ *     C_g = min(512, the largest multiple of 64 with 8 (5 P q C_g + P (2 q^2 + q + q (q + 3) / 2)) <= 160 KiB)   (64 at P = 4, q = 8)
+ * samples at a time, a function of (P, q) alone; the value's order does not depend on it.  No atomics on a value or an adjoint:
+ * per (wave, sample) the terms are added in walk order and cell order, the four slices in slice order, the samples of a
+ * 64-block by the fixed butterfly, blocks and chunks ascending.  Every output of a batch depends on its own moments, eps,
+ * jitter and the partition only -- not on G, its position in the call or the handle's history -- and identical calls return
+ * identical bits.
+ *   tgp_qehvi_moments_grad: tgp_qehvi_moments with the adjoints: val [G], gmean [P,G,q], gcov [P,G,q,q] objective-major; cov
+ *     is taken as given (no clip rule).  Any G >= 0, chunks of at most 2^28 / (16 P q (q + 1)) groups (moments and adjoints
+ *     within 256 MiB); checks, TGP_ERR_NOT_PD and TGP_ERR_STATE as tgp_qehvi_moments.
+ *   tgp_qehvi_value_grad: Xq [G,q,d] -> val [G], grad [G,q,d]; G >= 1 and G q <= 2048, else TGP_ERR_SHAPE (callers chunk, as for
+ *     tgp_joint_vjp); handle checks of tgp_qehvi_values.  Per handle, on its own stream, tgp_joint_forward's arrays into the
+ *     leading handle's stacked moments; the gradient tail on the leading stream (a diagonal entry of gcov[j] is zero where
+ *     handle j's variance was clipped at 1e-12); per handle tgp_joint_vjp's second half on the SAME K*^T and W K*; the P
+ *     gradients added in the order j = 0 .. P-1.  ONE host synchronisation.
+ * tgp_ehvi_last_ms reports the tail kernel's time for both (posterior time 0). */
 #define TGP_QEHVI_MAX_Q 8
 int tgp_qehvi_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
                       double jitter, double* out, int where);
 int tgp_qehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t G, int q, const double* eps, int S, double jitter,
                      double* out, int where);
+int tgp_qehvi_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
+                           double jitter, double* val, double* gmean, double* gcov, int where);
+int tgp_qehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t G, int q, const double* eps, int S,
+                         double jitter, double* val, double* grad, int where);
 
 /* == BatchReparametrizationSampler.sample (sampler.py:208-287) itself: out [G,S,q] = mean +
  * (chol(cov + jitter*I) eps)^T for Xq [G,q,d], eps [q,S].  q <= 64. */

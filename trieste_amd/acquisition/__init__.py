@@ -20,7 +20,7 @@ from .interface import (AcquisitionFunctionBuilder, AcquisitionFunctionClass, Gr
                         SingleModelVectorizedAcquisitionBuilder, VectorizedAcquisitionFunctionBuilder)
 from .multi_objective import (BatchMonteCarloExpectedHypervolumeImprovement, DividedAndConquerNonDominated,
                               ExactPartition2dNonDominated, ExpectedHypervolumeImprovement, Pareto, batch_ehvi,
-                              differentiable_expected_hv_improvement, expected_hv_improvement,
+                              differentiable_batch_ehvi, differentiable_expected_hv_improvement, expected_hv_improvement,
                               get_reference_point, non_dominated,
                               prepare_default_non_dominated_partition_bounds)
 from .optimizer import (FailedOptimizationError, automatic_optimizer_selector, batchify_joint, batchify_vectorize,

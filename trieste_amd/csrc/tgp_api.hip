@@ -3500,6 +3500,18 @@ int qehvi_enqueue_tail(tgp_handle h, const double* dmean, const double* dcov, in
   return TGP_OK;
 }
 
+// the gradient tail likewise: dval [gc], dgm [P][gstride][q], dgc [P][gstride][q][q]
+int qehvi_enqueue_grad_tail(tgp_handle h, const double* dmean, const double* dcov, int64_t gc, int64_t gstride, int q,
+                            const double* deps, int S, double jitter, int zero_clipped, double* dval, double* dgm, double* dgc) {
+  const double* db = h->d_ehvi.as<double>();
+  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_qehvi_grad_tail(h->stream, h->ehvi_P, h->ehvi_V, db, dc, h->ehvi_K, dmean, dcov, gc, gstride, q, deps, S, jitter,
+                         zero_clipped, dval, dgm, dgc, h->d_info.as<int>());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return TGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3585,6 +3597,144 @@ int tgp_qehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t G, i
   h->ehvi_tail_ms = h->last_ms;
   h->last_ms = sweep_ms;
   return rc;
+}
+
+// ---- the batch Monte-Carlo EHVI's gradient: qehvi_grad_tail_kernel on given moments, and tgp_ehvi_value_grad's body around it ------
+int tgp_qehvi_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
+                           double jitter, double* val, double* gmean, double* gcov, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = ehvi_need_partition(h)) return rc;
+  if (int rc = qehvi_check(h, G, q, eps, S, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!mean || !cov || !val || !gmean || !gcov) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  const int P = h->ehvi_P;
+  const int64_t qq = (int64_t)q * q;
+  const double* deps;
+  if (int rc = stage_in(h, h->s_in2, eps, (size_t)P * q * S, where, &deps)) return rc;
+  // (moments and adjoints of a chunk within 256 MiB: half of tgp_qehvi_moments' groups)
+  const int64_t chunk = std::max<int64_t>(1, qehvi_group_chunk(P, q) / 2);
+  const int rc = for_group_chunks(h, G, chunk, true, QEHVI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    // host residency: the moments through s_out1 / s_out2 as in tgp_qehvi_moments, the value through s_out3, the two adjoints
+    // through s_in and s_ent (idle in a call on given moments), objective j's groups of this chunk behind each other: [P][gc]
+    const double *dmean = mean + g0 * q, *dcov = cov + g0 * qq;
+    double *dval, *dgm = gmean + g0 * q, *dgc = gcov + g0 * qq;
+    int64_t gstride = G;
+    if (where != TGP_DEVICE) {
+      HIPCHK(h, h->s_out1.reserve((size_t)P * gc * q * sizeof(double)));
+      HIPCHK(h, h->s_out2.reserve((size_t)P * gc * qq * sizeof(double)));
+      HIPCHK(h, h->s_in.reserve((size_t)P * gc * q * sizeof(double)));
+      HIPCHK(h, h->s_ent.reserve((size_t)P * gc * qq * sizeof(double)));
+      for (int j = 0; j < P; ++j) {
+        HIPCHK(h, hipMemcpyAsync(h->s_out1.as<double>() + (size_t)j * gc * q, mean + ((int64_t)j * G + g0) * q,
+                                 (size_t)gc * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->s_out2.as<double>() + (size_t)j * gc * qq, cov + ((int64_t)j * G + g0) * qq,
+                                 (size_t)gc * qq * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      }
+      dmean = h->s_out1.as<double>();
+      dcov = h->s_out2.as<double>();
+      dgm = h->s_in.as<double>();
+      dgc = h->s_ent.as<double>();
+      gstride = gc;
+    }
+    if (int rb = stage_out_prepare(h, h->s_out3, val + g0, (size_t)gc, where, &dval)) return rb;
+    if (int rb = qehvi_enqueue_grad_tail(h, dmean, dcov, gc, gstride, q, deps, S, jitter, 0, dval, dgm, dgc)) return rb;
+    if (where != TGP_DEVICE)
+      for (int j = 0; j < P; ++j) {
+        HIPCHK(h, hipMemcpyAsync(gmean + ((int64_t)j * G + g0) * q, dgm + (size_t)j * gc * q, (size_t)gc * q * sizeof(double),
+                                 hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(gcov + ((int64_t)j * G + g0) * qq, dgc + (size_t)j * gc * qq, (size_t)gc * qq * sizeof(double),
+                                 hipMemcpyDeviceToHost, h->stream));
+      }
+    return stage_out_finish(h, dval, val + g0, (size_t)gc, where);
+  });
+  h->ehvi_sweep_ms = 0.0;
+  h->ehvi_tail_ms = h->last_ms;
+  return rc;
+}
+
+// tgp_ehvi_value_grad at q > 1.  Per member, on the member's own stream: the forward half of the joint posterior (K*^T, W K*,
+// the Gram product, the small-predict tail, the pick kernel) into the leading handle's stacked moments; on the leading stream
+// the gradient tail; per member again the backward half (joint_backward) on the SAME K*^T and W K* with (gmean_j, gcov_j) as
+// adjoints; on the leading stream the sum over the members.  The streams are ordered by each handle's ev_order; the one host
+// synchronisation is the leading stream's.
+int tgp_qehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t G, int q, const double* eps, int S,
+                         double jitter, double* val, double* grad, int where) {
+  if (!hs || !hs[0]) return TGP_ERR_ARG;
+  tgp_handle h = hs[0];
+  if (int rc = ehvi_check_stack(hs, P)) return rc;
+  if (int rc = qehvi_check(h, G, q, eps, S, jitter)) return rc;
+  if (G < 1 || G * (int64_t)q > JOINT_SMALL_P)
+    return fail(h, TGP_ERR_SHAPE, "G * q = %lld points: 1..%lld per call (chunk the groups)", (long long)(G * q),
+                (long long)JOINT_SMALL_P);
+  if (!Xq || !val || !grad) return fail(h, TGP_ERR_ARG, "Xq / val / grad is NULL");
+  if (int rc = set_device(h)) return rc;
+  const int d = h->d;
+  const int64_t M = G * (int64_t)q, Ppad = ((M + 63) / 64) * 64;
+  const size_t pm = (size_t)P * M, md = (size_t)M * d;
+  // every reservation first: a buffer that grows frees its old memory, which no stream may still be using
+  const double *dXq, *deps;
+  double *dval, *dgrad, *dmean, *dcov, *dgm, *dgc, *dparts;
+  if (int rc = stage_in(h, h->s_in, Xq, md, where, &dXq)) return rc;
+  if (int rc = stage_in(h, h->s_in2, eps, (size_t)P * q * S, where, &deps)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out2, grad, md, where, &dgrad)) return rc;
+  if (int rc = carve(h, h->s_ehvi, {{&dmean, pm}, {&dcov, pm * q}, {&dgm, pm}, {&dgc, pm * q}, {&dparts, (size_t)P * md}})) return rc;
+  HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  JointScratch w[EHVI_MAX_P];
+  bool shared[EHVI_MAX_P];   // the member is this handle a second time: its arrays are overwritten between the two halves
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    shared[j] = false;
+    for (int i = 0; i < P; ++i) shared[j] = shared[j] || (i != j && hs[i] == t);
+    const size_t np = (size_t)t->Npad * Ppad;
+    const size_t part = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, t->dp));
+    w[j] = JointScratch{};
+    if (int rc = carve(t, t->s_grad, {{&w[j].B, np}, {&w[j].C1, np}, {&w[j].T, np}, {&w[j].Z, np}, {&w[j].S, (size_t)Ppad * Ppad},
+                                      {&w[j].part, part}})) {
+      if (t != h) h->err = t->err;
+      return rc;
+    }
+  }
+  auto member = [&](tgp_handle t, int rc) {   // errors are reported on the leading handle
+    if (rc && t != h) h->err = t->err;
+    return rc;
+  };
+  // `from`'s stream so far happens before whatever `to`'s stream is given next
+  auto order = [&](tgp_handle from, tgp_handle to) -> int {
+    if (from->stream == to->stream) return TGP_OK;
+    HIPCHK(h, hipEventRecord(from->ev_order, from->stream));
+    HIPCHK(h, hipStreamWaitEvent(to->stream, from->ev_order, 0));
+    return TGP_OK;
+  };
+  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    if (int rc = order(h, t)) return rc;   // the staged points
+    if (int rc = member(t, joint_forward(t, w[j], dXq, M, Ppad, q, dmean + (size_t)j * M, dcov + (size_t)j * M * q))) return rc;
+    if (int rc = order(t, h)) return rc;
+  }
+  if (int rc = qehvi_enqueue_grad_tail(h, dmean, dcov, G, G, q, deps, S, jitter, 1, dval, dgm, dgc)) return rc;
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    if (int rc = order(h, t)) return rc;   // the adjoints
+    if (shared[j])
+      if (int rc = member(t, kstar_products(t, model_dev(t), t->d_W.as<double>(), t->Npad, dXq, M, Ppad, w[j].B, w[j].C1)))
+        return rc;
+    if (int rc = member(t, joint_backward(t, w[j], dXq, M, Ppad, q, dgm + (size_t)j * M, dgc + (size_t)j * M * q,
+                                          dparts + (size_t)j * md)))
+      return rc;
+    if (int rc = order(t, h)) return rc;
+  }
+  launch_ehvi_sum_parts(h->stream, dparts, P, (int64_t)md, dgrad);
+  if (int rc = stage_out_finish(h, dval, val, (size_t)G, where)) return rc;
+  if (int rc = stage_out_finish(h, dgrad, grad, md, where)) return rc;
+  if (int rc = sync(h)) return rc;
+  ehvi_read_tail_ms(h);
+  h->ehvi_sweep_ms = 0.0;
+  h->last_ms = 0.0;
+  h->last_launches = P;
+  return info_finish(h, QEHVI_NOT_PD);
 }
 
 int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms) {

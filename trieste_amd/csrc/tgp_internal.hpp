@@ -324,6 +324,16 @@ size_t qehvi_lds_bytes(int P, int q, int S);
 void launch_qehvi_tail(hipStream_t s, int P, int V, const double* bounds, const uint32_t* cells, int K, const double* mean,
                        const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
                        double* out, int* info);
+// the value with the adjoints of the joint moments: val [G], gmean [P][gstride][q], gcov [P][gstride][q][q] symmetric;
+// zero_clipped: a diagonal entry of gcov is zero where cov's sits at the posterior's floor.  Besides the samples the LDS holds
+// one adjoint copy per slice: samples per pass = the largest multiple of 64, at most 512, with
+// 8 (5 P q C + P (2 q q + q + q (q + 3) / 2)) <= 160 KiB (64 at P = 4, q = 8)
+constexpr int QEHVI_GRAD_LDS = 160 * 1024;
+int qehvi_grad_sample_chunk(int P, int q);
+size_t qehvi_grad_lds_bytes(int P, int q, int S);
+void launch_qehvi_grad_tail(hipStream_t s, int P, int V, const double* bounds, const uint32_t* cells, int K, const double* mean,
+                            const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
+                            int zero_clipped, double* val, double* gmean, double* gcov, int* info);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

@@ -152,6 +152,271 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_tail_kernel(const double*
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same value with its adjoints w.r.t. the joint moments ("the gradient"): gmean [P][gstride][q],
+// gcov [P][gstride][q][q] symmetric, objective-major like the inputs -- what tgp_joint_vjp takes per objective.
+//
+//   term of (cell k, subset J)   sign(J) prod_j n_J[j],  n_J[j] = min_{i in J} a[i][j]
+//   d term / d y[s,i*,j]         -sign(J) prod_{j' != j} n_J[j'], where i* is the point of J that attains the minimum in objective
+//                                j (strict comparison: the first point in walk order wins a tie) and only where
+//                                lb < y[s,i*,j] < ub strictly (a clamped sample contributes nothing)
+//   ybar[s,i,j]                  sum over cells and subsets;  gmean[j,i] = (1/S) sum_s ybar;  Lbar_j = (1/S) tril(sum_s ybar eps^T)
+//   gcov[j]                      L_j^-T sym(Phi(L_j^T Lbar_j)) L_j^-1 (qei_grad_tail_kernel's form); zero_clipped: a diagonal
+//                                entry of cov at VAR_FLOOR gets zero
+//
+// Phases 1 and 2 and the value's sums are qehvi_tail_kernel's, operation for operation: a lane adds its (64-block, cell) sums in
+// the same order whatever the chunk, so the smaller chunk here (qehvi_grad_sample_chunk) leaves the value's bits alone.
+//   phase 3      the walk also carries, per level and objective, WHICH level of the path owns the running minimum (0: nobody --
+//                the owner's sample sits at or below the cell's lower bound).  Every level has P accumulators in registers (the
+//                template recursion's frames: "the adjoint of the point at this level"); a live term adds its P partial
+//                products into the owning levels through a compile-time-unrolled select, and a level flushes its accumulators
+//                into THIS WAVE's Ybar[j][i][lane] when its loop leaves point i (i is wave-uniform, the column lane-private)
+//   phase 4a     per chunk: ybar = ((Ybar_0 + Ybar_1) + Ybar_2) + Ybar_3 (slice order); wave w takes the entries w, w + 4, ... of
+//                (gmean[j][i], Lbar_j[i][m <= i]): lane = sample, the fixed butterfly per 64-block, lane 0 adds the blocks
+//                (ascending) and chunks (ascending) into the entry's LDS slot
+//   phase 4b     wave j: the Cholesky adjoint of objective j, lane c = column c / row c; then coalesced stores
+// No atomics touch a value, every order above is a function of (P, q, S, K) alone, nothing read depends on G or g.
+//   LDS          8 (5 P q C' + P (2 q q + q + q (q + 3) / 2)) bytes, C' = min(C, S rounded up to 64), C = qehvi_grad_sample_chunk(P, q):
+//                the samples and four adjoint copies, the factors, the means, the work matrices, the sums; up to 160 KiB, so
+//                one workgroup per CU (a call has at most 2048 / q groups)
+template <int P>
+struct QehviAdj {
+  double g[QEHVI_MAX_Q][P];
+};
+
+template <int P, int D>
+__device__ __forceinline__ void qehvi_walk_grad(const double* Ys, double* Yb, int ldi, int ldj, const double (&lb)[P],
+                                                const double (&ub)[P], const double (&m)[P], const int (&own)[P], int first,
+                                                int q, double& c, QehviAdj<P>& A) {
+  for (int i = first; i < q; ++i) {
+    double n[P];
+    int o[P];
+    bool live = true;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      const double y = Ys[j * ldj + i * ldi];
+      const double a = ub[j] - fmin(fmax(y, lb[j]), ub[j]);
+      n[j] = fmin(m[j], a);
+      o[j] = a < m[j] ? (y > lb[j] ? D : 0) : own[j];
+      live = live && n[j] > 0.0;
+    }
+    if (live) {
+      double t = n[0];
+#pragma unroll
+      for (int j = 1; j < P; ++j) t *= n[j];
+      c = (D & 1) ? c + t : c - t;
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        double p = 1.0;   // prod_{j' != j} n[j'], ascending j'
+        bool started = false;
+#pragma unroll
+        for (int j2 = 0; j2 < P; ++j2)
+          if (j2 != j) {
+            p = started ? p * n[j2] : n[j2];
+            started = true;
+          }
+        const double v = (D & 1) ? -p : p;
+#pragma unroll
+        for (int l = 1; l <= D; ++l) A.g[l - 1][j] += o[j] == l ? v : 0.0;
+      }
+      if constexpr (D < QEHVI_MAX_Q) qehvi_walk_grad<P, D + 1>(Ys, Yb, ldi, ldj, lb, ub, n, o, i + 1, q, c, A);
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        Yb[j * ldj + i * ldi] += A.g[D - 1][j];
+        A.g[D - 1][j] = 0.0;
+      }
+    }
+  }
+}
+
+template <int P>
+__global__ __launch_bounds__(QEHVI_THREADS) void qehvi_grad_tail_kernel(
+    const double* __restrict__ mean, const double* __restrict__ cov, int64_t gstride, int q, const double* __restrict__ eps, int S,
+    int chunk, double jitter, const double* __restrict__ bounds, int V, const uint32_t* __restrict__ cells, int K,
+    int zero_clipped, double* __restrict__ val, double* __restrict__ gmean, double* __restrict__ gcov, int* __restrict__ info) {
+  extern __shared__ double qehvi_lds[];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t g = blockIdx.x;
+  const int qq = q * q;
+  const int nent = q * (q + 3) / 2;    // per objective: q means and q (q + 1) / 2 entries of Lbar's lower triangle
+  const int rowcap = min(chunk, (S + 63) & ~63);
+  double* const Ls = qehvi_lds;        // [P][q][q]
+  double* const mu = Ls + P * qq;      // [P][q]
+  double* const Ms = mu + P * q;       // [P][q][q]: Lbar -> ... -> gcov, in place
+  double* const Es = Ms + P * qq;      // [P][nent]: the sums over the samples
+  double* const Y = Es + P * nent;     // [P][q][rowcap]; afterwards [4][64] partial sums
+  double* const Yb = Y + P * q * rowcap;   // [4][P][q][rowcap]: one adjoint copy per wave
+
+  // phase 1: moments in, P factorisations (qehvi_tail_kernel's)
+  for (int e = tid; e < P * qq; e += QEHVI_THREADS) {
+    const int j = e / qq, r = e - j * qq, i = r / q, k = r - i * q;
+    Ls[e] = cov[((int64_t)j * gstride + g) * qq + r] + (i == k ? jitter : 0.0);
+  }
+  for (int e = tid; e < P * q; e += QEHVI_THREADS) {
+    const int j = e / q;
+    mu[e] = mean[((int64_t)j * gstride + g) * q + (e - j * q)];
+  }
+  for (int e = tid; e < P * nent; e += QEHVI_THREADS) Es[e] = 0.0;
+  __syncthreads();
+  if (tid < P) {
+    double* const A = Ls + tid * qq;
+    for (int j = 0; j < q; ++j) {
+      double dj = A[j * q + j];
+      if (!(dj > 0.0)) {
+        atomicCAS(info, 0, (int)(g % 2000000000) + 1);
+        dj = 1.0;
+      }
+      const double sd = sqrt(dj);
+      A[j * q + j] = sd;
+      for (int i = j + 1; i < q; ++i) A[i * q + j] = A[i * q + j] / sd;
+      for (int i = j + 1; i < q; ++i) {
+        const double nl = -A[i * q + j];
+        for (int k = j + 1; k <= i; ++k) A[i * q + k] = fma(nl, A[k * q + j], A[i * q + k]);
+      }
+    }
+  }
+  __syncthreads();
+
+  double acc = 0.0;
+  QehviAdj<P> A;   // every level flushes and clears its own slots before its loop moves on: cleared once, here
+#pragma unroll
+  for (int l = 0; l < QEHVI_MAX_Q; ++l)
+#pragma unroll
+    for (int j = 0; j < P; ++j) A.g[l][j] = 0.0;
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cs = min(chunk, S - s0);       // samples of this chunk
+    const int ld = (cs + 63) & ~63;          // row length in LDS (<= rowcap)
+    const int pql = P * q * ld;
+    // phase 2: the chunk's samples, the adjoint copies cleared
+    for (int e = tid; e < pql; e += QEHVI_THREADS) {
+      const int ji = e / ld, s = e - ji * ld;
+      const int j = ji / q, i = ji - j * q;
+      double y = 0.0;
+      if (s < cs) {
+        y = mu[ji];
+        const double* const Lr = Ls + j * qq + i * q;
+        const double* const ep = eps + (int64_t)j * q * S + s0 + s;
+        for (int m2 = 0; m2 <= i; ++m2) y = fma(Lr[m2], ep[(int64_t)m2 * S], y);
+      }
+      Y[e] = y;
+    }
+    for (int e = tid; e < QEHVI_WAVES * pql; e += QEHVI_THREADS) Yb[e] = 0.0;
+    __syncthreads();
+    // phase 3: the cells of slice `wave` for the samples lane, lane + 64, ...
+    double* const Ybw = Yb + wave * pql;
+    for (int b = 0; b < ld; b += 64) {
+      const bool valid = b + lane < cs;
+      const double* const Ys = Y + b + lane;
+      for (int k = wave; k < K; k += QEHVI_WAVES) {
+        double lb[P], ub[P], top[P];
+        int nobody[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          const uint32_t w = cells[(size_t)k * P + j];
+          lb[j] = fmax(bounds[j * V + (int)(w & 0xffffu)], -1e10);
+          ub[j] = bounds[j * V + (int)(w >> 16)];
+          top[j] = INFINITY;
+          nobody[j] = 0;
+        }
+        double c = 0.0;
+        if (valid) qehvi_walk_grad<P, 1>(Ys, Ybw + b + lane, ld, q * ld, lb, ub, top, nobody, 0, q, c, A);
+        acc += c;
+      }
+    }
+    __syncthreads();
+    // phase 4a: this chunk's part of gmean and Lbar
+    for (int e = wave; e < P * nent; e += QEHVI_WAVES) {
+      const int j = e / nent, r = e - j * nent;   // r < q: gmean[j][r]; else the r - q th entry (i, m <= i) of the triangle
+      int i = r, m2 = -1;
+      if (r >= q) {
+        int t = r - q;
+        i = 0;
+        while (t > i) {
+          t -= i + 1;
+          ++i;
+        }
+        m2 = t;
+      }
+      const double* const y0 = Yb + (j * q + i) * ld;
+      const double* const ep = eps + ((int64_t)j * q + (m2 < 0 ? 0 : m2)) * S + s0;
+      double sum = 0.0;
+      for (int b = 0; b < ld; b += 64) {
+        const int s = b + lane;
+        double v = 0.0;
+        if (s < cs) {
+          v = ((y0[s] + y0[pql + s]) + y0[2 * pql + s]) + y0[3 * pql + s];
+          if (m2 >= 0) v *= ep[s];
+        }
+        sum += wave_sum(v);
+      }
+      if (lane == 0) Es[e] += sum;
+    }
+    __syncthreads();
+  }
+  Y[tid] = acc;   // [slice][lane]
+  // Lbar's lower triangle into Ms, scaled; the means' adjoints out
+  const double invS = 1.0 / (double)S;
+  for (int e = tid; e < P * nent; e += QEHVI_THREADS) {
+    const int j = e / nent, r = e - j * nent;
+    const double v = Es[e] * invS;
+    if (r < q) {
+      gmean[((int64_t)j * gstride + g) * q + r] = v;
+    } else {
+      int t = r - q, i = 0;
+      while (t > i) {
+        t -= i + 1;
+        ++i;
+      }
+      Ms[j * qq + i * q + t] = v;
+    }
+  }
+  __syncthreads();
+  if (tid < 64) {
+    double sum = Y[tid];
+    for (int w = 1; w < QEHVI_WAVES; ++w) sum += Y[w * 64 + tid];
+    sum = wave_sum(sum);
+    if (tid == 0) val[g] = sum / (double)S;
+  }
+  // phase 4b: wave j takes objective j (P <= 4 waves); lane c owns column c, later row c (qei_grad_tail_kernel's steps)
+  const bool work = wave < P && lane < q;
+  const double* const L = Ls + (wave < P ? wave : 0) * qq;
+  double* const M = Ms + (wave < P ? wave : 0) * qq;
+  if (work)   // Q = tril(L^T Lbar) in place, rows ascending; R's lower triangle = Q / 2
+    for (int a = lane; a < q; ++a) {
+      double t = 0.0;
+      for (int k = a; k < q; ++k) t = fma(L[k * q + a], M[k * q + lane], t);
+      M[a * q + lane] = 0.5 * t;
+    }
+  __syncthreads();
+  if (work)
+    for (int a = 0; a < lane; ++a) M[a * q + lane] = M[lane * q + a];   // R = R^T
+  __syncthreads();
+  if (work)   // L^-T R: back substitution down column c
+    for (int a = q - 1; a >= 0; --a) {
+      double t = M[a * q + lane];
+      for (int k = a + 1; k < q; ++k) t = fma(-L[k * q + a], M[k * q + lane], t);
+      M[a * q + lane] = t / L[a * q + a];
+    }
+  __syncthreads();
+  if (work) {   // ... L^-1: back substitution along row r
+    double* const row = M + lane * q;
+    for (int a = q - 1; a >= 0; --a) {
+      double t = row[a];
+      for (int k = a + 1; k < q; ++k) t = fma(-L[k * q + a], row[k], t);
+      row[a] = t / L[a * q + a];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < P * qq; e += QEHVI_THREADS) {
+    const int j = e / qq, r = e - j * qq, i = r / q, k = r - i * q;
+    const int64_t at = ((int64_t)j * gstride + g) * qq + r;
+    // (zero_clipped: a variance at the posterior's floor was clipped there, and the clip's adjoint is zero)
+    // (the two substitutions leave a matrix that is symmetric to rounding: its symmetric part, in bits)
+    gcov[at] = zero_clipped && i == k && !(cov[at] > VAR_FLOOR) ? 0.0 : 0.5 * (Ms[e] + Ms[j * qq + k * q + i]);
+  }
+}
+
 template <int P>
 void launch_qehvi_p(hipStream_t s, int V, const double* bounds, const uint32_t* cells, int K, const double* mean,
                     const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter, double* out,
@@ -159,6 +424,18 @@ void launch_qehvi_p(hipStream_t s, int V, const double* bounds, const uint32_t* 
   const int chunk = qehvi_sample_chunk(P, q);
   hipLaunchKernelGGL(qehvi_tail_kernel<P>, dim3((unsigned)G), dim3(QEHVI_THREADS), qehvi_lds_bytes(P, q, S), s, mean, cov, gstride,
                      q, eps, S, chunk, jitter, bounds, V, cells, K, out, info);
+}
+
+template <int P>
+void launch_qehvi_grad_p(hipStream_t s, int V, const double* bounds, const uint32_t* cells, int K, const double* mean,
+                         const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
+                         int zero_clipped, double* val, double* gmean, double* gcov, int* info) {
+  // per launch, as launch_qei_grad_tail_qp: the attribute belongs to the current device, and one process may drive several; a
+  // failure shows as the launch's error, which every caller checks
+  (void)hipFuncSetAttribute((const void*)qehvi_grad_tail_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, QEHVI_GRAD_LDS);
+  hipLaunchKernelGGL(qehvi_grad_tail_kernel<P>, dim3((unsigned)G), dim3(QEHVI_THREADS), qehvi_grad_lds_bytes(P, q, S), s, mean, cov,
+                     gstride, q, eps, S, qehvi_grad_sample_chunk(P, q), jitter, bounds, V, cells, K, zero_clipped, val, gmean, gcov,
+                     info);
 }
 
 }  // namespace
@@ -181,6 +458,32 @@ void launch_qehvi_tail(hipStream_t s, int P, int V, const double* bounds, const 
   if (P == 2) launch_qehvi_p<2>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, out, info);
   else if (P == 3) launch_qehvi_p<3>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, out, info);
   else launch_qehvi_p<4>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, out, info);
+}
+
+// doubles beside the sample slots: the factors, the means, the adjoint work matrices, the sums of gmean and Lbar
+static size_t qehvi_grad_fixed_doubles(int P, int q) { return (size_t)P * (2 * q * q + q + q * (q + 3) / 2); }
+
+int qehvi_grad_sample_chunk(int P, int q) {
+  const int fit = (int)((QEHVI_GRAD_LDS - 8 * qehvi_grad_fixed_doubles(P, q)) / (8 * (QEHVI_SLICES + 1) * P * q)) & ~63;
+  return fit < QEHVI_MAX_CHUNK ? fit : QEHVI_MAX_CHUNK;
+}
+
+size_t qehvi_grad_lds_bytes(int P, int q, int S) {
+  const int chunk = qehvi_grad_sample_chunk(P, q), padded = (int)(((int64_t)S + 63) & ~(int64_t)63);
+  // (the [4][64] partial sums of the value fit the sample slots: 5 P q 64 >= 640 doubles)
+  return 8 * (qehvi_grad_fixed_doubles(P, q) + (size_t)(QEHVI_SLICES + 1) * P * q * (padded < chunk ? padded : chunk));
+}
+
+void launch_qehvi_grad_tail(hipStream_t s, int P, int V, const double* bounds, const uint32_t* cells, int K, const double* mean,
+                            const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
+                            int zero_clipped, double* val, double* gmean, double* gcov, int* info) {
+  if (G <= 0) return;
+  if (P == 2)
+    launch_qehvi_grad_p<2>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, zero_clipped, val, gmean, gcov, info);
+  else if (P == 3)
+    launch_qehvi_grad_p<3>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, zero_clipped, val, gmean, gcov, info);
+  else
+    launch_qehvi_grad_p<4>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, zero_clipped, val, gmean, gcov, info);
 }
 
 }  // namespace tgp

@@ -1037,3 +1037,61 @@ def qehvi_values(engines, Xq, eps, jitter: float = 1e-6):
     engines[0]._chk(engines[0]._lib.tgp_qehvi_values(hs, len(engines), a.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter), po,
                                                      a.where))
     return out
+
+
+QEHVI_GRAD_MAX_POINTS = 2048  # points (groups x q) per tgp_qehvi_value_grad call (callers chunk)
+
+
+def qehvi_grad_sample_chunk(P: int, q: int) -> int:
+    """Samples the qEHVI gradient kernel keeps in LDS at a time: besides the samples one adjoint slot per sample and cell
+    slice, next to the factors, the means, the adjoint work matrices and the sums of gmean and Lbar -- the largest multiple
+    of 64, at most 512, with 8 (5 P q C + P (2 q^2 + q + q (q + 3) / 2)) <= 160 KiB.  A function of (P, q) alone; 64 at
+    P = 4, q = 8."""
+    fixed = P * (2 * q * q + q + q * (q + 3) // 2)
+    return min(512, ((160 * 1024 - 8 * fixed) // (8 * (QEHVI_SLICES + 1) * P * q)) // 64 * 64)
+
+
+def qehvi_grad_sum_roundings(P: int, q: int, S: int, K: int) -> int:
+    """The rounding count of one adjoint entry of the qEHVI gradient kernel ahead of the Cholesky adjoint:
+    2 P - 3 per partial product (its P - 1 factors and their P - 2 products); the at most 2^(q-1) terms of a (sample, cell)
+    that hold a point, once into a level's register sum and once per flush of a level into the wave's slot, over the cells of
+    a slice; the 3 additions over the slices, the product with eps, the 6 of the butterfly, the 64-blocks, and the scaling
+    by 1 / S (two roundings)."""
+    return (2 * P - 3) + 2 ** (q - 1) * (1 + -(-K // QEHVI_SLICES)) + 3 + 1 + 6 + -(-S // 64) + 2
+
+
+def qehvi_moments_grad(engine, mean, cov, eps, jitter: float = 1e-6):
+    """The qEHVI tail with the adjoints of the joint moments on caller-supplied moments: mean [P, ..., q], cov [P, ..., q, q]
+    objective-major, eps [P, q, S] -> (value [...], gmean [P, ..., q], gcov [P, ..., q, q] symmetric)
+    (tgp_qehvi_moments_grad).  The value is :func:`qehvi_moments`' bit for bit.  Needs a partition and no data."""
+    m, c = _Arg(mean), _Arg(cov)
+    if len(m.shape) < 2 or c.shape != m.shape + (m.shape[-1],):
+        raise ValueError(f"mean must be [P, ..., q] and cov [P, ..., q, q], got {m.shape} and {c.shape}")
+    if m.where != c.where:
+        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    P, lead, q = m.shape[0], m.shape[1:-1], m.shape[-1]
+    G = int(np.prod(lead)) if lead else 1
+    e = _qehvi_eps(P, q, eps, m.where)
+    val, pv = GPEngine._out(m, lead)
+    gm, pgm = GPEngine._out(m, m.shape)
+    gc, pgc = GPEngine._out(m, c.shape)
+    engine._chk(engine._lib.tgp_qehvi_moments_grad(engine._h, m.ptr, c.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter), pv, pgm,
+                                                   pgc, m.where))
+    return val, gm, gc
+
+
+def qehvi_value_grad(engines, Xq, eps, jitter: float = 1e-6):
+    """engines: one :class:`GPEngine` per objective (the first carries the partition); Xq [G, q, d] with 1 <= G and
+    G q <= 2048, eps [P, q, S] -> (qEHVI [G], its gradient [G, q, d]) in one device call: every engine's joint posterior,
+    the gradient tail, every engine's vector-Jacobian product and their sum (tgp_qehvi_value_grad)."""
+    engines, hs = _handles(engines)
+    a = _Arg(Xq)
+    if len(a.shape) != 3 or a.shape[2] != engines[0].d:
+        raise ValueError(f"Xq must be [G, q, {engines[0].d}], got shape {tuple(a.shape)}")
+    G, q = int(a.shape[0]), int(a.shape[1])
+    e = _qehvi_eps(len(engines), q, eps, a.where)
+    val, pv = GPEngine._out(a, (G,))
+    grad, pg = GPEngine._out(a, tuple(a.shape))
+    engines[0]._chk(engines[0]._lib.tgp_qehvi_value_grad(hs, len(engines), a.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter),
+                                                         pv, pg, a.where))
+    return val, grad
