@@ -1,5 +1,6 @@
 """The numpy side of the float32 pre-screen of the pruned EI arg-max (TEST INFRASTRUCTURE; tests/test_prescreen_cases.py on
-the CPU, tests/test_gpu_prune_prescreen.py on the GPU).  DESIGN.md 4.1 has the derivation.
+the CPU, tests/test_gpu_prune_prescreen.py on the GPU; on general models tests/test_prune_general_cases.py and
+tests/test_gpu_prune_general.py).  DESIGN.md 4.1 has the derivation.
 
 Phase 0 forms every candidate's posterior mean in float32 kernel arithmetic,
 
@@ -123,7 +124,8 @@ def block_quantities(eta, variance, m32, E):
     """-> (ub32 [blocks], prebest): the pre-screen's bound per 128-candidate block and its lower seed over all of them."""
     m = m32.shape[0]
     nblk = -(-m // PC.CAND_BLOCK)
-    ok = (E <= variance) & np.isfinite(m32)
+    with np.errstate(over="ignore"):
+        ok = (E * E <= variance) & np.isfinite(m32)      # E above the prior standard deviation says nothing
     with np.errstate(all="ignore"):
         t = PC.ei_tail(eta - (m32 - E), np.full_like(m32, max(variance, O.VAR_FLOOR)))
     ub = np.where(ok & ~np.isnan(t), np.maximum(t * TAIL_INFLATE, MIN_BOUND), np.inf)
@@ -168,3 +170,7 @@ def restated_blocks(name, label, Xq):
 # at least half of the oracle's S.RECORDED[name]["screened"][label] (tests/test_prescreen_cases.py recomputes it)
 SHARE_CASE = ("m52_N512_d8", "eta")
 SHARE_DISMISSED = 1024
+# The same on a general model, one whose variance (1e-4) lies below every E: under a cap E <= variance, a length compared
+# with its square, phase 0 dismissed nothing here (tests/test_prune_general_cases.py recomputes the count)
+SHARE_CASE_GENERAL = ("g_m32_d3_N513_small", "eta+3")
+SHARE_DISMISSED_GENERAL = 1023

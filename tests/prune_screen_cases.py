@@ -13,6 +13,7 @@ Once a 128-candidate block's posterior means are known, the bloc
 The best word a block sees is the largest of its own seed and of the seeds and finished maxima of the blocks that came
 ``lag`` or more places before it in the order the blocks are taken."""
 import functools
+import math
 
 import numpy as np
 from scipy.linalg import cho_solve, solve_triangular
@@ -27,18 +28,27 @@ NBLK = -(-PC.M // PC.CAND_BLOCK)
 
 
 def threshold(name, label):
-    """The EI threshold of a case: the model's eta, eta shifted up (more and larger seeds), or so low that every EI is 0."""
-    eta = PC.oracle_state(name)[1]
-    return {"eta": eta, "eta+0.5": eta + 0.5, "eta+3": eta + 3.0, "-1e6": -1e6}[label]
+    """The EI threshold of a case: the model's eta, eta shifted up (more and larger seeds) by 0.5 and 3 prior standard
+    deviations, or so low that every EI is 0."""
+    return thresholds(PC.problem(name), PC.oracle_state(name)[1])[label]
+
+
+def thresholds(p, eta):
+    """The four thresholds of a model p (variance, mean_const) around `eta`; at variance 1 and mean 0: eta, eta + 0.5,
+    eta + 3 and -1e6 bit for bit."""
+    sd = math.sqrt(p.variance)
+    return {"eta": eta, "eta+0.5": eta + 0.5 * sd, "eta+3": eta + 3.0 * sd, "-1e6": -1e6 * sd + p.mean_const}
 
 
 @functools.lru_cache(maxsize=None)
-def sample_moments(name):
+def sample_moments(name, bound_variance=None):
     """-> (mean [SAMPLE], var [nrb][SAMPLE]) of the first SAMPLE plain candidates: var[i] the variance bound after row
-    blocks 0 .. i (var[-1]: the variance), as tests/prune_cases.partial_bounds forms them.  Read-only."""
+    blocks 0 .. i (var[-1]: the variance), as tests/prune_cases.partial_bounds forms them.  Read-only.
+    ``bound_variance`` plants a defect: the checkpoints' bounds var[:-1] taken from it in place of the model's variance."""
     st, _ = PC.oracle_state(name)
     Xq = PC.candidates(name)[:SAMPLE]
-    K = O.kernel_matrix(st.kind, st.variance, st.lengthscales, st.X, Xq)
+    with PC.form(name):
+        K = O.kernel_matrix(st.kind, st.variance, st.lengthscales, st.X, Xq)
     A = solve_triangular(st.L, K, lower=True)
     mean = solve_triangular(st.L.T, A, lower=False).T @ st.err + st.mean_const
     nrb = -(-st.N // PC.ROW_BLOCK)
@@ -46,6 +56,8 @@ def sample_moments(name):
     sq[: st.N] = A * A
     cum = np.cumsum(sq.reshape(nrb, PC.ROW_BLOCK, -1).sum(1), 0)
     var = np.maximum(st.variance - cum, O.VAR_FLOOR)
+    if bound_variance is not None:
+        var[:-1] = np.maximum(bound_variance - cum[:-1], O.VAR_FLOOR)
     mean.setflags(write=False)
     var.setflags(write=False)
     return mean, var
@@ -58,8 +70,9 @@ def full_means(name):
     alpha = cho_solve((st.L, True), st.err)
     Xq = PC.candidates(name)
     out = np.empty(Xq.shape[0])
-    for lo in range(0, Xq.shape[0], 8192):
-        out[lo: lo + 8192] = O.kernel_matrix(st.kind, st.variance, st.lengthscales, Xq[lo: lo + 8192], st.X) @ alpha
+    with PC.form(name):
+        for lo in range(0, Xq.shape[0], 8192):
+            out[lo: lo + 8192] = O.kernel_matrix(st.kind, st.variance, st.lengthscales, Xq[lo: lo + 8192], st.X) @ alpha
     out += st.mean_const
     out.setflags(write=False)
     return out
@@ -79,14 +92,18 @@ def block_seeds(eta, mean):
     return diff.reshape(nblk, PC.CAND_BLOCK).max(1)
 
 
-def sweep_with_screen(mean, var, eta, variance, order, lag):
+def sweep_with_screen(mean, var, eta, variance, order, lag, bound_mean=None):
     """Seed, mean screen and block-stop rule over var [nrb][M], the blocks taken in `order` (a permutation of the block
-    numbers).  -> (winner value, winner index, given_up [blocks] bool, screened [blocks] bool, seed [blocks])."""
+    numbers).  -> (winner value, winner index, given_up [blocks] bool, screened [blocks] bool, seed [blocks]).
+    ``bound_mean`` plants a defect: seeds, screen and checkpoint bounds taken at it, the values at the mean."""
     nrb, m = var.shape
     nblk = -(-m // PC.CAND_BLOCK)
     ub = PC.ei_tail((eta - mean)[None, :], var)
-    ub0 = screen_bound(eta, mean, variance)
-    seed = block_seeds(eta, mean)
+    if bound_mean is not None:
+        ub[:-1] = PC.ei_tail((eta - bound_mean)[None, :], var[:-1])
+    bmean = mean if bound_mean is None else bound_mean
+    ub0 = screen_bound(eta, bmean, variance)
+    seed = block_seeds(eta, bmean)
     known_at = np.full(nblk, -np.inf)     # by position: what the block there contributed to the best word
     given = np.zeros(nblk, dtype=bool)
     screened = np.zeros(nblk, dtype=bool)
@@ -173,3 +190,38 @@ RECORDED = {
 # (name, label) for which the oracle screens at least half of the blocks: there the GPU test asks the engine for half of
 # the oracle's count
 SHARE_CASES = [(n, t) for n in PC.SHARE_IDS for t in THRESHOLDS if 2 * RECORDED[n]["screened"][t] >= NBLK]
+
+
+def oracle_winner(name, label):
+    """-> (index, value): the oracle's EI arg-max over the whole plain set at a threshold (first index on ties)."""
+    st, _ = PC.oracle_state(name)
+    Xq = PC.candidates(name)
+    ei = np.empty(Xq.shape[0])
+    with PC.form(name):
+        for lo in range(0, Xq.shape[0], 8192):
+            ei[lo: lo + 8192] = O.ei_values(st, Xq[lo: lo + 8192], threshold(name, label))
+    i = int(O.argmax_first(ei))
+    return i, float(ei[i])
+
+
+# The same for the general models of tests/prune_cases.GENERAL, every oracle call in the difference form
+# (tests/test_prune_general_cases.py recomputes every entry), and besides
+#   eta         the oracle's eta
+#   winner      oracle_winner(name, "eta+0.5"): (index, value), what the GPU test anchors its unpruned launch to
+RECORDED_GENERAL = {
+    "g_m52_d8_N512_at1024": dict(screened={"eta": 0, "eta+0.5": 584, "eta+3": 761, "-1e6": 0}, top_seed=98678, dup_blocks=(300, 1023),
+                                 eta=-33.85038789307664, winner=(98678, 10.24761699070908)),
+    "g_rbf_d6_N700_at100": dict(screened={"eta": 756, "eta+0.5": 761, "eta+3": 767, "-1e6": 0}, top_seed=120794, dup_blocks=(300, 1023),
+                                eta=34.92427399671836, winner=(120794, 1.0065885234340541)),
+    "g_m32_d3_N513_small": dict(screened={"eta": 720, "eta+0.5": 753, "eta+3": 758, "-1e6": 0}, top_seed=5637, dup_blocks=(300, 1023),
+                                eta=-1000.0750091284492, winner=(5637, 0.009564162937749643)),
+    "g_m12_d5_N600_neg": dict(screened={"eta": 0, "eta+0.5": 0, "eta+3": 750, "-1e6": 0}, top_seed=111006, dup_blocks=(300, 1023),
+                              eta=-93.26201392883644, winner=(111006, 0.009862664064817922)),
+    "g_m52_d16_N700_lownoise": dict(screened={"eta": 0, "eta+0.5": 0, "eta+3": 666, "-1e6": 0}, top_seed=25629, dup_blocks=(300, 1023),
+                                    eta=33.139741719016506, winner=(25629, 0.0004205607549843723)),
+    "g_m32_d4_N520_var1e4": dict(screened={"eta": 691, "eta+0.5": 750, "eta+3": 762, "-1e6": 0}, top_seed=9084, dup_blocks=(300, 1023),
+                                 eta=-463.5020323334269, winner=(9084, 91.97766486373574)),
+}
+# A test may ask the engine for a share of the oracle's screened count only where the oracle screens at least half of the
+# blocks.  These (name, label) qualify; every general model has one (eta + 3 sd)
+SHARE_CASES_GENERAL = [(n, t) for n in PC.GENERAL_IDS for t in THRESHOLDS if 2 * RECORDED_GENERAL[n]["screened"][t] >= NBLK]

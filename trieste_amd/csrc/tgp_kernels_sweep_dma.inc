@@ -595,8 +595,10 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
 //   E = |alpha|_1 variance (1.0625 u [..] + 2^-53 [2 G1 (|Xs_0| + S) + 256 + Npad] + 2^-60) + 2^-50 (|mean32| + |eta|)
 // (1/16 for the second-order terms; the 2^-53 term for the float64 side -- centring, the exact pass's own rounding; 2^-60
 // for flushed float32 denormals: at most DP squares below 2^-126 are lost, 2^-61 on sqrt(q); the last term for the
-// roundings of mean32 - E and eta - mean32).  A block with a candidate whose E is not finite or exceeds the variance, or
-// whose mean32 is not finite, gets +inf and posts no lower seed.
+// roundings of mean32 - E and eta - mean32).  A block with a candidate whose E is not finite or exceeds the prior standard
+// deviation (E * E > variance: E is a length in output units, the variance its square, so the cap must compare like with
+// like -- E <= variance switched phase 0 off for every model whose outputs are scaled down), or whose mean32 is not
+// finite, gets +inf and posts no lower seed.
 template <int KIND>
 struct PreShape {
   static constexpr double G1 = KIND == KIND_RBF ? 0.72 : KIND == KIND_M12 ? 0.70 : KIND == KIND_M32 ? 0.26 : 0.20;
@@ -696,7 +698,7 @@ __global__ __launch_bounds__(1024, 8) void prune_prescreen_kernel(const SweepArg
           pl.e_out[cand] = E;
         }
         ub = INFINITY;
-        if (E <= variance && fabs(m32) < INFINITY) {   // (a NaN compares false)
+        if (E * E <= variance && fabs(m32) < INFINITY) {   // (a NaN compares false; an overflowing square is +inf)
           const double t = acq_tail(ACQ_EI, a.acq_param, m32 - E, fmax(variance, VAR_FLOOR), a.m.noise);
           if (!(t != t)) ub = fmax(t * PRE_TAIL_INFLATE, PRE_MIN_BOUND);
           seed = ((a.acq_param - m32) - E) * (1.0 - 0x1p-50);   // rounded down
