@@ -564,41 +564,82 @@ CLAMP_LB = 1e-8  # entropy.py:47
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
+MILLS_U0 = 6.0
+
+
+def _mills_cf(u):
+    """Laplace's continued fraction of the hazard h(u) = pdf(u) / Phi(-u), u > MILLS_U0: h = u + delta,
+    delta = 1 / (u + t_2), t_k = k / (u + t_{k+1}), sixteen levels, as csrc/tgp_dev.hpp evaluates it (x = 1 / u,
+    q_k = q_{k+1} + (k + 1) x^2 q_{k+2}).  -> (delta, t_2, t_3 - t_2)."""
+    x = 1.0 / u
+    x2 = x * x
+    q = {17: np.ones_like(x), 18: np.zeros_like(x)}
+    for k in range(16, 0, -1):
+        q[k] = (k + 1) * x2 * q[k + 2] + q[k + 1]
+    return x * q[2] / q[1], 2.0 * x * q[3] / q[2], x * (3.0 * q[4] * q[2] - 2.0 * q[3] * q[3]) / (q[3] * q[2])
+
+
 def log_normal_cdf(x):
-    """tfp.distributions.Normal(0, 1).log_cdf = special_math.log_ndtr for float64 (tensorflow-probability 0.24,
-    special_math.py): x > 8: -ndtr(-x);  -20 <= x <= 8: log(ndtr(x));  x < -20: asymptotic series of order 3,
-    -x^2/2 - log(-x) - log(2 pi)/2 + log(1 - 1/x^2 + 3/x^4 - 15/x^6)."""
+    """log Phi(x), the mathematical function in both tails.  (tfp.distributions.Normal(0, 1).log_cdf, which the reference
+    calls, is -ndtr(-x) above 8 and an order-3 asymptotic series below -20: 5e-6 relative at x = -20.5.  DESIGN.md,
+    "Entropy tails".)  x >= 0: log1p(-Phi(-x));  -6 <= x < 0: log Phi(x);  below: -x^2/2 - log(2 pi)/2 - log h(-x)."""
     x = np.asarray(x, dtype=np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        mid = np.log(_ndtr(np.clip(x, -20.0, 8.0)))
-        hi = -_ndtr(-np.maximum(x, 8.0))
-        xl = np.minimum(x, -20.0)
-        x2 = xl * xl
-        lo = -0.5 * x2 - np.log(-xl) - _HALF_LOG_2PI + np.log(1.0 - 1.0 / x2 + 3.0 / x2 ** 2 - 15.0 / x2 ** 3)
-    return np.where(x > 8.0, hi, np.where(x >= -20.0, mid, lo))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        hi = np.log1p(-_ndtr(-np.maximum(x, 0.0)))
+        mid = np.log(_ndtr(np.clip(x, -MILLS_U0, 0.0)))
+        xl = np.minimum(x, -MILLS_U0)
+        lo = -0.5 * xl * xl - _HALF_LOG_2PI - np.log(_mills_cf(-xl)[0] - xl)
+    return np.where(x >= 0.0, hi, np.where(x >= -MILLS_U0, mid, lo))
 
 
-def _gamma_ratio(mean, var, samples):
+def entropy_sample_terms(gamma):
+    """Per-sample pieces of the entropy tails at u = gamma, free of the u^2 cancellations of the reference's float64
+    formulas (csrc/tgp_dev.hpp, entropy_tail): with h = pdf(u) / Phi(-u), delta = h - u, w = 1 - h delta
+    -> (h, h delta, w, 1 - u delta, (h delta)', -u h / 2 - log Phi(-u))."""
+    u = np.asarray(gamma, dtype=np.float64)
+    big = u > MILLS_U0
+    ub = np.where(big, u, 2.0 * MILLS_U0)
+    us = np.where(big, 0.0, u)
+    delta, t2, t32 = _mills_cf(ub)
+    hb = ub + delta
+    wb = delta * (t2 - delta)
+    fb = -0.5 * ub * delta + _HALF_LOG_2PI + np.log(hb)
+    with np.errstate(under="ignore"):
+        hs = normal_pdf(us) / _ndtr(-us)
+        ds = hs - us
+        hds = hs * ds
+        ws = 1.0 - hds
+        fs = -0.5 * us * hs - log_normal_cdf(-us)
+        dhds = hs * (ds * ds - ws)
+    return (np.where(big, hb, hs), np.where(big, 1.0 - wb, hds), np.where(big, wb, ws),
+            np.where(big, t2 * delta, 1.0 - us * ds), np.where(big, hb * delta * delta * t2 * t32, dhds),
+            np.where(big, fb, fs))
+
+
+def _gamma(mean, var, samples):
     fsd = np.maximum(np.sqrt(var), CLAMP_LB)                       # clip below (entropy.py:201-204)
-    gamma = (np.asarray(samples, dtype=np.float64).reshape(1, -1) - np.asarray(mean)[:, None]) / fsd[:, None]
-    log_minus_cdf = log_normal_cdf(-gamma)
-    ratio = np.exp(-0.5 * gamma * gamma - _HALF_LOG_2PI - log_minus_cdf)   # exp(log_prob(gamma) - log_cdf(-gamma))
-    return gamma, log_minus_cdf, ratio
+    return (np.asarray(samples, dtype=np.float64).reshape(1, -1) - np.asarray(mean)[:, None]) / fsd[:, None]
+
+
+def _gibbon_terms(gamma, var, noise):
+    """(g, dg/du, dg/d rho^2) [M, S] of g = -1/2 log(1 + rho^2 h (u - h)) = -1/2 log((1 - rho^2) + rho^2 w)."""
+    _, hd, w, _, dhd, _ = entropy_sample_terms(gamma)
+    rho2 = (var / (var + noise))[:, None]
+    inner = (noise / (var + noise))[:, None] + rho2 * w
+    g = np.where(hd < 0.5, -0.5 * np.log1p(-rho2 * np.minimum(hd, 0.5)), -0.5 * np.log(inner))
+    return g, 0.5 * rho2 * dhd / inner, 0.5 * hd / inner
 
 
 def min_value_entropy_search(mean, var, samples) -> np.ndarray:
     """min_value_entropy_search.__call__ (entropy.py:195-214): mean [M], var [M] (predict's), samples [S]."""
-    gamma, log_minus_cdf, ratio = _gamma_ratio(np.asarray(mean), np.asarray(var), samples)
-    return np.mean(-gamma * ratio / 2.0 - log_minus_cdf, axis=1)
+    gamma = _gamma(np.asarray(mean), np.asarray(var, dtype=np.float64), samples)
+    return np.mean(entropy_sample_terms(gamma)[5], axis=1)
 
 
 def gibbon_quality_term(mean, var, samples, noise) -> np.ndarray:
     """gibbon_quality_term.__call__ (entropy.py:479-500)."""
     var = np.asarray(var, dtype=np.float64)
-    rho_squared = var / (var + noise)
-    gamma, _, ratio = _gamma_ratio(np.asarray(mean), var, samples)
-    inner_log = 1.0 + rho_squared[:, None] * ratio * (gamma - ratio)
-    return -0.5 * np.mean(np.log(inner_log), axis=1)
+    return np.mean(_gibbon_terms(_gamma(np.asarray(mean), var, samples), var, noise)[0], axis=1)
 
 
 def gibbon_repulsion_term(state: GPRState, x: np.ndarray, pending: np.ndarray, rescaled_repulsion: bool = True):
@@ -622,8 +663,8 @@ def entropy_value_and_grad(state: GPRState, acq: str, samples, Xq, twin: Optiona
                            weight: float = 0.0):
     """Value [P] and gradient [P, d] of the MES / GIBBON acquisition at Xq -- what autodiff through
     min_value_entropy_search / GibbonAcquisition hands L-BFGS-B -- analytically.  With u = gamma,
-    r = pdf(u) / Phi(-u): dr/du = r (r - u);  MES: f = -u r / 2 - log Phi(-u), df/du = r/2 - u r (r - u) / 2;
-    GIBBON: g = -1/2 log(1 + rho^2 h), h = r (u - r), dh/du = -r (u - r)^2 + r - r^2 (r - u);
+    h = pdf(u) / Phi(-u), delta = h - u, w = 1 - h delta: dh/du = h delta;  MES: f = -u h / 2 - log Phi(-u),
+    df/du = h (1 - u delta) / 2;  GIBBON: g = -1/2 log(1 - rho^2 h delta), (h delta)' = h (delta^2 - w);
     du/dmean = -1/sd, du/dvar = -u / (2 var), d rho^2 / dvar = noise / (var + noise)^2.  The repulsion term (twin =
     the state conditioned on the pending points) adds weight/2 (log(var_twin + noise) - log(var + noise))."""
     Xq = np.asarray(Xq, dtype=np.float64)
@@ -638,19 +679,13 @@ def entropy_value_and_grad(state: GPRState, acq: str, samples, Xq, twin: Optiona
     mu, var, dmu, dvar = mean_var_grads(state)
     sd_raw = np.sqrt(var)
     clamped = ~(sd_raw > CLAMP_LB)
-    gamma, lmc, r = _gamma_ratio(mu, var, samples)
+    gamma = _gamma(mu, var, samples)
     if acq == "mes":
-        f = -gamma * r / 2.0 - lmc
-        fu = r / 2.0 - gamma * r * (r - gamma) / 2.0
+        h, _, _, one_ud, _, f = entropy_sample_terms(gamma)
+        fu = 0.5 * h * one_ud
         frho = np.zeros_like(f)
     else:
-        rho2 = (var / (var + state.noise))[:, None]
-        h = r * (gamma - r)
-        inner = 1.0 + rho2 * h
-        dh = -r * (gamma - r) ** 2 + r - r * r * (r - gamma)
-        f = -0.5 * np.log(inner)
-        fu = -0.5 * rho2 * dh / inner
-        frho = -0.5 * h / inner
+        f, fu, frho = _gibbon_terms(gamma, var, state.noise)
     sd = np.maximum(sd_raw, CLAMP_LB)
     val = f.mean(axis=1)
     dv_dmu = -fu.mean(axis=1) / sd

@@ -50,10 +50,17 @@ class P:
     """One configuration's problem."""
 
 
+def problem(cfg):
+    """The problem of a configuration: a name from ``CONFIGS``, or a configuration of another module's list (``_cfg``)."""
+    if isinstance(cfg, str):
+        cfg = next(c for c in CONFIGS if c["name"] == cfg)
+    return _problem(tuple(cfg.items()))
+
+
 @functools.lru_cache(maxsize=None)
-def problem(name):
-    cfg = next(c for c in CONFIGS if c["name"] == name)
-    d, N = cfg["d"], cfg["N"]
+def _problem(items):
+    cfg = dict(items)
+    name, d, N = cfg["name"], cfg["d"], cfg["N"]
     rng = np.random.default_rng(4321)
     X = rng.uniform(size=(N, d))
     f = O.ackley(X)
@@ -273,16 +280,17 @@ def coefficient_partials(p, acq, param, mean, var):
             bm * aug + cdf * daug, bv * aug + 2.0 * pdf / (2.0 * sd) * daug + ei * d2aug)
 
 
-def gradient_check(p, acq, param, grad, mean, var, dmean_dx, dvar_dx):
+def gradient_check(p, acq, param, grad, mean, var, dmean_dx, dvar_dx, coefficients=None, partials=None):
     """Compare gradients [P, d] with the chain rule at the moments given: ref = a dmean/dx + b dvar/dx with (a, b) from
-    ``grad_coefficients`` at (mean, var) and the oracle's moment gradients.  Per row, the tolerance is 1e-5 |ref|_inf
+    ``grad_coefficients`` at (mean, var) (or ``coefficients``, with their ``partials`` in the order of
+    ``coefficient_partials``: another module's tails) and the oracle's moment gradients.  Per row, the tolerance is 1e-5 |ref|_inf
     plus the first-order change of (a, b) under 8 ulp of the moments; that term must stay below 1e-6 |ref|_inf.  Rows with
     sd < 0.05 sqrt(variance) are not compared; rows whose reference gradient is below 1e-290 must be finite and below 1e-290
     themselves.  -> (err, tol, asserted rows, ref, problems)."""
     grad = np.asarray(grad, dtype=np.float64)
-    a, b = grad_coefficients(p, acq, param, mean, var)
+    a, b = grad_coefficients(p, acq, param, mean, var) if coefficients is None else coefficients
     ref = a[:, None] * dmean_dx + b[:, None] * dvar_dx
-    am, av, bm, bv = coefficient_partials(p, acq, param, mean, var)
+    am, av, bm, bv = coefficient_partials(p, acq, param, mean, var) if partials is None else partials
     dm, dv = 8.0 * EPS * np.abs(mean), 8.0 * EPS * var
     sens = (am * dm + av * dv)[:, None] * np.abs(dmean_dx) + (bm * dm + bv * dv)[:, None] * np.abs(dvar_dx)
     scale = np.abs(ref).max(axis=1)

@@ -250,26 +250,59 @@ __device__ __forceinline__ double acq_tail(int acq, double param, double mean, d
   }
 }
 
-// ---- (value, index) ordering: larger value wins, ties -> smaller index (tf.math.argmax) -----
-// NaN never wins (TF's argmax would propagate NaN; a NaN acquisition value is an upstream bug).
-// log Phi(x), stable in both tails -- tfp.distributions.Normal.log_cdf (special_math.log_ndtr, float64):
-// x > 8: -Phi(-x);  -20 <= x <= 8: log Phi(x);  x < -20: the asymptotic series of order 3
-//   -x^2/2 - log(-x) - log(2 pi)/2 + log(1 - 1/x^2 + 3/x^4 - 15/x^6).
+// Laplace's continued fraction of the hazard h(u) = pdf(u) / Phi(-u) for u > MILLS_U0:
+//   h = u + delta,  delta = 1 / (u + t_2),  t_k = k / (u + t_{k+1}),
+// sixteen levels (t_17 = 0) without a division per level: with x = 1 / u and q_k = q_{k+1} + (k + 1) x^2 q_{k+2}
+// (q_17 = 1, q_18 = 0; every term positive, nothing cancels), t_k = k x q_{k+1} / q_k and delta = x q_2 / q_1.
+// Returns delta, t_2 and t_3 - t_2: what the entropy tails need of h - u, 1 - h (h - u) and its derivative without
+// subtracting two terms of size u^2.  At u = 6 the truncation is below 1e-13 of delta.
+constexpr double MILLS_U0 = 6.0;
+__device__ __forceinline__ void mills_cf(double u, double& delta, double& t2, double& t32) {
+  const double x = 1.0 / u, x2 = x * x;
+  double qa = 1.0, qb = 0.0;   // q_{k+1}, q_{k+2}
+#pragma unroll
+  for (int k = 16; k >= 5; --k) {
+    const double q = fma((double)(k + 1) * x2, qb, qa);
+    qb = qa;
+    qa = q;
+  }
+  const double q4 = fma(5.0 * x2, qb, qa);
+  const double q3 = fma(4.0 * x2, qa, q4);
+  const double q2 = fma(3.0 * x2, q4, q3);
+  const double q1 = fma(2.0 * x2, q3, q2);
+  delta = x * q2 / q1;
+  t2 = 2.0 * x * q3 / q2;
+  t32 = x * (3.0 * q4 * q2 - 2.0 * q3 * q3) / (q3 * q2);
+}
+
+// log Phi(x), the mathematical function to float64 in both tails (tfp's log_ndtr, which the reference calls, loses it:
+// DESIGN.md, "Entropy tails"):  x >= 0: log1p(-Phi(-x));  -MILLS_U0 <= x < 0: log Phi(x);  below: with u = -x,
+// Phi(-u) = pdf(u) / h(u), -u^2/2 - log(2 pi)/2 - log h(u).
 __device__ __forceinline__ double log_normal_cdf(double x) {
-  if (x > 8.0) return -normal_cdf(-x);
-  if (x >= -20.0) return log(normal_cdf(x));
-  const double x2 = x * x;
-  return -0.5 * x2 - log(-x) - 0.9189385332046727 + log(1.0 - 1.0 / x2 + 3.0 / (x2 * x2) - 15.0 / (x2 * x2 * x2));
+  if (x >= 0.0) return log1p(-normal_cdf(-x));
+  if (x >= -MILLS_U0) return log(normal_cdf(x));
+  double delta, t2, t32;
+  mills_cf(-x, delta, t2, t32);
+  return -0.5 * x * x - 0.9189385332046727 - log(delta - x);
 }
 
 // Entropy-search tails on (mean, var) and the min-value samples s_1..s_S (reference
-// acquisition/function/entropy.py): with gamma_s = (s - mean) / sd, sd = max(sqrt(var), 1e-8) (CLAMP_LB :47),
-// ratio = pdf(gamma) / Phi(-gamma) computed as exp(log pdf - log Phi(-gamma)):
-//   ACQ_MES     (min_value_entropy_search.__call__ :195-214): mean_s [-gamma ratio / 2 - log Phi(-gamma)]
-//   ACQ_GIBBON  (gibbon_quality_term.__call__ :479-500):      -1/2 mean_s log(1 + rho^2 ratio (gamma - ratio)),
+// acquisition/function/entropy.py): with u_s = gamma_s = (s - mean) / sd, sd = max(sqrt(var), 1e-8) (CLAMP_LB :47),
+// h = pdf(u) / Phi(-u):
+//   ACQ_MES     (min_value_entropy_search.__call__ :195-214): mean_s [-u h / 2 - log Phi(-u)]
+//   ACQ_GIBBON  (gibbon_quality_term.__call__ :479-500):      -1/2 mean_s log(1 + rho^2 h (u - h)),
 //                                                              rho^2 = var / (var + noise)
 //   ACQ_LOGYVAR: log(var + noise) -- the two halves of GIBBON's repulsion term (:580-619)
 // Returns the value and its partial derivatives w.r.t. mean and var (for the L-BFGS-B refinement).
+// Per sample, in terms of delta = h - u > 0 and w = 1 - h delta in (0, 1) (the variance of the truncated normal):
+//   dh/du = h delta;  MES: f = -u h / 2 - log Phi(-u), df/du = h (1 - u delta) / 2;
+//   GIBBON: g = -1/2 log(1 - rho^2 h delta) = -1/2 log((1 - rho^2) + rho^2 w), dg/du = rho^2 (h delta)' / (2 inner),
+//   (h delta)' = h (delta^2 - w), dg/d rho^2 = h delta / (2 inner).
+// u <= MILLS_U0: h from erfc; the differences lose eps u^2 (values) to eps u^6 (derivatives): below 2e-10 at u = 6.
+// u > MILLS_U0: from the continued fraction, where u delta = 1 - t_2 delta:
+//   f = -u delta / 2 + log(2 pi)/2 + log h;  1 - u delta = t_2 delta;  w = delta (t_2 - delta);
+//   delta^2 - w = delta^2 t_2 (t_3 - t_2)  -- no term of size u^2 is formed, so gamma = 1e8 is as good as gamma = 10.
+// u < 0: log Phi(-u) = log1p(-Phi(u)), and 1 - rho^2 h delta through log1p (h delta -> 0: the value is ~ rho^2 h |u| / 2).
 __device__ __forceinline__ void entropy_tail(int acq, double mean, double var, double noise,
                                              const double* __restrict__ samples, int S, double& v,
                                              double& dv_dmu, double& dv_dvar) {
@@ -283,22 +316,38 @@ __device__ __forceinline__ void entropy_tail(int acq, double mean, double var, d
   const bool clamped = !(sd_raw > 1e-8);
   const double sd = clamped ? 1e-8 : sd_raw;
   const double rho2 = var / (var + noise);
+  const double nrho2 = noise / (var + noise);   // 1 - rho^2
   double acc = 0.0, acc_u = 0.0, acc_rho = 0.0, acc_uu = 0.0;
   for (int t = 0; t < S; ++t) {
     const double u = (samples[t] - mean) / sd;
-    const double lmc = log_normal_cdf(-u);
-    const double r = exp(-0.5 * u * u - 0.9189385332046727 - lmc);
-    double f, fu;  // per-sample value and d/du;  dr/du = r (r - u)
-    if (acq == ACQ_MES) {
-      f = -0.5 * u * r - lmc;
-      fu = 0.5 * r - 0.5 * u * r * (r - u);
+    double h, hd, w, one_ud, dhd, fmes;   // h delta, 1 - h delta, 1 - u delta, (h delta)', the MES term
+    if (u > MILLS_U0) {
+      double delta, t2, t32;
+      mills_cf(u, delta, t2, t32);
+      h = u + delta;
+      w = delta * (t2 - delta);
+      hd = 1.0 - w;
+      one_ud = t2 * delta;
+      dhd = h * delta * delta * t2 * t32;
+      fmes = -0.5 * u * delta + 0.9189385332046727 + log(h);
     } else {
-      const double hh = r * (u - r);
-      const double inner = 1.0 + rho2 * hh;
-      const double dh = -r * (u - r) * (u - r) + r - r * r * (r - u);
-      f = -0.5 * log(inner);
-      fu = -0.5 * rho2 * dh / inner;
-      acc_rho += -0.5 * hh / inner;  // d/d rho^2
+      h = normal_pdf(u) / normal_cdf(-u);
+      const double delta = h - u;
+      hd = h * delta;
+      w = 1.0 - hd;
+      one_ud = 1.0 - u * delta;
+      dhd = h * (delta * delta - w);
+      fmes = -0.5 * u * h - log_normal_cdf(-u);
+    }
+    double f, fu;  // per-sample value and d/du
+    if (acq == ACQ_MES) {
+      f = fmes;
+      fu = 0.5 * h * one_ud;
+    } else {
+      const double inner = nrho2 + rho2 * w;
+      f = hd < 0.5 ? -0.5 * log1p(-rho2 * hd) : -0.5 * log(inner);
+      fu = 0.5 * rho2 * dhd / inner;
+      acc_rho += 0.5 * hd / inner;  // d/d rho^2
     }
     acc += f;
     acc_u += fu;
@@ -312,6 +361,8 @@ __device__ __forceinline__ void entropy_tail(int acq, double mean, double var, d
   if (acq == ACQ_GIBBON) dv_dvar += acc_rho * inv * noise / ((var + noise) * (var + noise));
 }
 
+// ---- (value, index) ordering: larger value wins, ties -> smaller index (tf.math.argmax) -----
+// NaN never wins (TF's argmax would propagate NaN; a NaN acquisition value is an upstream bug).
 __device__ __forceinline__ bool better(double v, int64_t i, double bv, int64_t bi) {
   return (v > bv) || (v == bv && i < bi);
 }
