@@ -438,6 +438,26 @@ def test_handles_on_streams_of_their_own_return_the_same_bits():
             np.testing.assert_array_equal(dg.cpu().numpy(), want[1])
 
 
+@pytest.mark.parametrize("M", [5, 70])
+def test_a_handle_named_twice_answers_as_two_engines_of_its_own(M):
+    """A stack that names one handle twice, [a, b, a, b]: a handle's products are recomputed between its two appearances, so
+    the call returns the bits of [a, b, a2, b2] with a2, b2 separate engines of identical data and hyper-parameters.  M = 5
+    is one pad block, M = 70 one point past it."""
+    E = _E()
+    N, d, kernel = 40, 2, "matern52"
+    X, members = _stack_problem(2, N, d, kernel, seed=31)
+    a, b = _stack_engines(X, members, d, kernel)
+    a2, b2 = _stack_engines(X, members, d, kernel)
+    rng = np.random.default_rng(31)
+    E.ehvi_set_partition_tables(a, *T.table_partition(rng, 4, 6, 20))
+    Xq = rng.uniform(size=(M, d))
+    want = E.ehvi_value_grad([a, b, a2, b2], Xq)
+    got = E.ehvi_value_grad([a, b, a, b], Xq)
+    assert np.any(want[0] != 0.0) and np.any(want[1] != 0.0)
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(got[1], want[1])
+
+
 def test_a_set_precision_does_not_change_the_answer():
     """Float64 always: a stack whose handles are set to the int8 or ``auto`` precision answers with the same bits."""
     E = _E()

@@ -1,7 +1,8 @@
 """Development aid: checksums of what the host layer's small-call paths return (tgp_api.hip: the small-product posterior, the
 group-chunk loop, the calls on given moments) where tests/history_tour.py and tests/ehvi_tour.py do not reach -- host- AND
 device-resident arguments, a wide model, a repulsion twin whose padded size differs from the model's, G q = 2048 exactly, a
-tgp_qei of two chunks.  Run under two builds (TGP_LIB=...) and diff the output: a change that only moves host code or
+tgp_qei of two chunks, and every tgp_ehvi_* / tgp_qehvi_* entry on small stacks (both residencies, private streams, a handle
+named twice, a group that is not positive definite).  Run under two builds (TGP_LIB=...) and diff the output: a change that only moves host code or
 scratch addresses must leave every line identical."""
 import sys, os, hashlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -75,6 +76,85 @@ for where, put in (("host", lambda *xs: xs), ("dev", dev)):
     print("moments", where, "batch_ei_moments_grad", h(*E.batch_ei_moments_grad(eng, m, c, a1, a2, 0.3)))
     print("moments", where, "ehvi_moments", h(E.ehvi_moments(eng, pm, pv)), flush=True)
 eng.close()
+
+# the multi-objective entries (tgp_ehvi_*, tgp_qehvi_*) on small stacks: P = 2 and P = 4 members, N = 130, d = 3, a table
+# partition of a few dozen cells; host and device; every member on a private stream; one handle named twice; a group that
+# is not positive definite
+def stack(P, private=False):
+    out = []
+    for j in range(P):
+        Xj, Yj = O.synthetic_problem(O.ackley, 3, 130, 300 + j)
+        e = GPEngine(3, ("matern52", "rbf")[j % 2])
+        e.set_hyper(0.8 + 0.3 * j, O.default_lengthscales(3) * (1.0 + 0.1 * j), 1e-3 * (1 + j), 0.1 * j)
+        e.set_data(Xj, Yj)
+        if private:
+            e.use_private_stream()
+        out.append(e)
+    return out
+
+def table_partition(P, V=7, K=36):
+    bounds = np.sort(rng.uniform(0.0, 1.0, size=(P, V)), axis=1); bounds[:, 0] = -1e10
+    lo = rng.integers(0, V - 1, size=(K, P))
+    hi = lo + 1 + (rng.integers(0, V, size=(K, P)) % (V - 1 - lo))
+    return bounds, np.full(P, V, np.int32), lo.astype(np.int32), hi.astype(np.int32)
+
+def moments(P, G, q):
+    A = rng.standard_normal((P, G, q, q))
+    return rng.uniform(0.0, 1.0, (P, G, q)), A @ A.transpose(0, 1, 3, 2) / q + 0.05 * np.eye(q)
+
+def value_grads(p, engines, points, put):
+    """the two value-grad entries over ``points``: (M, [(q, S, G)])"""
+    P = len(engines)
+    for M in points[0]:
+        print(p, f"M={M} ehvi_value_grad", h(*E.ehvi_value_grad(engines, put(rng.uniform(size=(M, 3)))[0])))
+    for q, S, G in points[1]:
+        xg, e = put(rng.uniform(size=(G, q, 3)), rng.standard_normal((P, q, S)))
+        print(p, f"q={q} S={S} G={G} qehvi_value_grad", h(*E.qehvi_value_grad(engines, xg, e)), flush=True)
+
+QS = (1, 2, 4, E.QEHVI_MAX_Q)
+for P in (2, 4):
+    engines, part = stack(P), table_partition(P)
+    E.ehvi_set_partition_tables(engines[0], *part)
+    for where, put in (("host", lambda *xs: xs), ("dev", dev)):
+        p = f"stack P={P} {where}"
+        for M in (5, 70, 2048):
+            xq, pm, pv = put(rng.uniform(size=(M, 3)), rng.uniform(0.0, 1.0, (P, M)), 10.0 ** rng.uniform(-4, 0, (P, M)))
+            print(p, f"M={M} ehvi_values", h(E.ehvi_values(engines, xq)))
+            print(p, f"M={M} ehvi_argmax", h(*E.ehvi_argmax(engines, xq, index_base=3)))
+            print(p, f"M={M} ehvi_moments_grad", h(*E.ehvi_moments_grad(engines[0], pm, pv)))
+            print(p, f"M={M} ehvi_value_grad", h(*E.ehvi_value_grad(engines, xq)), flush=True)
+        for q in QS:
+            for S in (40, 200):
+                for G in (9, 170):
+                    mean, cov = moments(P, G, q)
+                    m, c, xg, e = put(mean, cov, rng.uniform(size=(G, q, 3)), rng.standard_normal((P, q, S)))
+                    pq = f"{p} q={q} S={S} G={G}"
+                    print(pq, "qehvi_moments", h(E.qehvi_moments(engines[0], m, c, e)))
+                    print(pq, "qehvi_moments_grad", h(*E.qehvi_moments_grad(engines[0], m, c, e)))
+                    print(pq, "qehvi_values", h(E.qehvi_values(engines, xg, e)))
+                    print(pq, "qehvi_value_grad", h(*E.qehvi_value_grad(engines, xg, e)), flush=True)
+            value_grads(p, engines, ((), [(q, 40, 2048 // q)]), put)   # G q = 2048 exactly
+    points = ((5, 70, 2048), [(q, S, G) for q in QS for S, G in ((40, 170), (200, 9))])
+    private = stack(P, private=True)
+    E.ehvi_set_partition_tables(private[0], *part)
+    value_grads(f"stack P={P} private streams", private, points, lambda *xs: xs)
+    for e in private:
+        e.close()
+    if P == 4:
+        value_grads("stack [a, b, a, b]", [engines[0], engines[1], engines[0], engines[1]], points, lambda *xs: xs)
+    # a group that is not positive definite: the code and the message of each moments entry
+    mean, cov = moments(P, 9, 4)
+    cov[P - 1, 5] = -cov[P - 1, 5]
+    e = rng.standard_normal((P, 4, 40))
+    for name, fn in (("qehvi_moments", E.qehvi_moments), ("qehvi_moments_grad", E.qehvi_moments_grad)):
+        try:
+            fn(engines[0], mean, cov, e)
+            said = "no error"
+        except Exception as err:
+            said = f"{type(err).__name__}: {err}"
+        print(f"stack P={P} not PD", name, hashlib.sha256(said.encode()).hexdigest()[:16], said, flush=True)
+    for e in engines:
+        e.close()
 
 # one wide model: the candidate tiles and the gradient tail's partial sums at dp = 48
 eng, X, Y = model(40, 300)

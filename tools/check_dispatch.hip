@@ -1,4 +1,5 @@
-// Host-only check of the padded-dimension / kernel-kind dispatch of tgp_internal.hpp: launches nothing, needs no GPU.
+// Host-only check of the padded-dimension / kernel-kind / objective-count dispatch of tgp_internal.hpp: launches nothing, needs
+// no GPU.
 //   hipcc -std=c++17 --offload-arch=gfx950 -I trieste_amd/csrc tools/check_dispatch.hip -o check_dispatch && ./check_dispatch
 // (development: add -Xarch_host -fsanitize=address,undefined; tests/test_dispatch.py builds and runs it plain)
 #include <cstdio>
@@ -62,6 +63,18 @@ int main() {
     EXPECT(got == k[1], "with_kind(%d) handed over %d", k[0], got);
     const int family[4] = {0, 1, 2, 3};
     EXPECT(by_kind(family, k[0]) == got, "with_kind(%d) and by_kind disagree", k[0]);
+  }
+
+  // with_objectives: every P of 2 .. EHVI_MAX_P reaches its own instantiation, once; anything else the last one
+  for (int P = -1; P <= EHVI_MAX_P + 3; ++P) {
+    int calls = 0;
+    const int got = with_objectives(P, [&](auto PC) {
+      static_assert(2 <= decltype(PC)::value && decltype(PC)::value <= EHVI_MAX_P, "no instantiation outside 2 .. EHVI_MAX_P");
+      ++calls;
+      return (int)decltype(PC)::value;
+    });
+    EXPECT(calls == 1 && got == (2 <= P && P <= EHVI_MAX_P ? P : EHVI_MAX_P), "with_objectives(%d) handed over %d in %d calls", P,
+           got, calls);
   }
 
   if (failures) {

@@ -3209,14 +3209,38 @@ int ehvi_need_partition(tgp_handle h) {
   return TGP_OK;
 }
 
-// the tail on device-resident moments [P][M] into dout [M], bracketed by the handle's events: enqueue only
-int ehvi_enqueue_tail(tgp_handle h, const double* dmean, const double* dvar, int64_t M, double* dout) {
+// the partition that tgp_set_ehvi_partition keeps on the handle, as the tail launchers take it: bounds [P][V] and the packed
+// cells [K][P] behind them on the device, the bound counts nb [P] on the host
+struct PartitionDev {
+  const double* bounds;
+  const uint32_t* cells;
+  int P, V, K;
+  const int* nb;
+};
+PartitionDev partition_dev(tgp_handle h) {
   const double* db = h->d_ehvi.as<double>();
-  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
+  return {db, (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V), h->ehvi_P, h->ehvi_V, h->ehvi_K, h->ehvi_nb};
+}
+
+// a launch on the handle's stream between its two events (ehvi_read_tail_ms and for_group_chunks read them): enqueue only
+template <class Launch>
+int bracketed(tgp_handle h, Launch launch) {
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  launch_ehvi_tail(h->stream, h->ehvi_P, h->ehvi_V, h->ehvi_nb, db, dc, h->ehvi_K, dmean, dvar, M, dout);
+  launch();
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   return TGP_OK;
+}
+
+// a member's status as the call's: the error belongs to the leading handle
+int member_rc(tgp_handle h, tgp_handle t, int rc) {
+  if (rc && t != h) h->err = t->err;
+  return rc;
+}
+
+// the tail on device-resident moments [P][M] into dout [M]
+int ehvi_enqueue_tail(tgp_handle h, const double* dmean, const double* dvar, int64_t M, double* dout) {
+  const PartitionDev p = partition_dev(h);
+  return bracketed(h, [&] { launch_ehvi_tail(h->stream, p.P, p.V, p.nb, p.bounds, p.cells, p.K, dmean, dvar, M, dout); });
 }
 
 void ehvi_read_tail_ms(tgp_handle h) {
@@ -3228,13 +3252,10 @@ void ehvi_read_tail_ms(tgp_handle h) {
 // the gradient tail likewise: dval [M], dgm / dgv [P][M]
 int ehvi_enqueue_grad_tail(tgp_handle h, const double* dmean, const double* dvar, int64_t M, int zero_clipped, double* dval,
                            double* dgm, double* dgv) {
-  const double* db = h->d_ehvi.as<double>();
-  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  launch_ehvi_grad_tail(h->stream, h->ehvi_P, h->ehvi_V, h->ehvi_nb, db, dc, h->ehvi_K, dmean, dvar, M, zero_clipped, dval, dgm,
-                        dgv);
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  return TGP_OK;
+  const PartitionDev p = partition_dev(h);
+  return bracketed(h, [&] {
+    launch_ehvi_grad_tail(h->stream, p.P, p.V, p.nb, p.bounds, p.cells, p.K, dmean, dvar, M, zero_clipped, dval, dgm, dgv);
+  });
 }
 
 // checks of the stack: errors are reported on the leading handle
@@ -3275,10 +3296,8 @@ int ehvi_stack_moments(const tgp_handle* hs, int P, const double* Xq, int64_t M,
   double sweep_ms = 0.0;
   for (int j = 0; j < P; ++j) {
     // (tgp_predict synchronises the member's stream before it returns: the tail below may run on any stream)
-    if (int rc = tgp_predict(hs[j], dXq, M, *dmean + (size_t)j * M, *dvar + (size_t)j * M, TGP_DEVICE)) {
-      if (hs[j] != h) h->err = hs[j]->err;
+    if (int rc = member_rc(h, hs[j], tgp_predict(hs[j], dXq, M, *dmean + (size_t)j * M, *dvar + (size_t)j * M, TGP_DEVICE)))
       return rc;
-    }
     if (hs[j]->last_launches > 0) {
       double ms = 0.0;
       (void)tgp_last_kernel_ms(hs[j], &ms, nullptr);
@@ -3289,6 +3308,76 @@ int ehvi_stack_moments(const tgp_handle* hs, int P, const double* Xq, int64_t M,
   h->ehvi_sweep_ms = sweep_ms;
   *dXq_out = dXq;
   return TGP_OK;
+}
+
+// The body of the two value-and-gradient calls over a stack, behind their checks and the staging of their inputs (dXq: the
+// M = G q points).  Per member, on the member's own stream: forward(j, t, w, dmean_j, dcov_j), the posterior's forward half
+// into the leading handle's stacked moments [P][M], [P][M][q], leaving K*^T and W K* in w; on the leading stream
+// tail(dmean, dcov, dval, dgm, dgc), the bracketed gradient tail; per member again the backward half (joint_backward) on the
+// SAME K*^T and W K* with (gmean_j, gcov_j) as adjoints; on the leading stream the sum over the members.  The streams are
+// ordered by each handle's ev_order; the one host synchronisation is the leading stream's.  gram: the forward half takes the
+// Gram array of JointScratch.  not_pd: the tail reports a breakdown through d_info (info_finish's message), nullptr: it
+// cannot fail.
+template <class Forward, class Tail>
+int stack_value_grad(const tgp_handle* hs, int P, const double* dXq, int64_t M, int64_t Ppad, int q, bool gram, const char* not_pd,
+                     double* val, double* grad, int where, Forward forward, Tail tail) {
+  tgp_handle h = hs[0];
+  const int64_t G = M / q;
+  const size_t pm = (size_t)P * M, md = (size_t)M * h->d;
+  // every reservation first: a buffer that grows frees its old memory, which no stream may still be using
+  double *dval, *dgrad, *dmean, *dcov, *dgm, *dgc, *dparts;
+  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
+  if (int rc = stage_out_prepare(h, h->s_out2, grad, md, where, &dgrad)) return rc;
+  if (int rc = carve(h, h->s_ehvi, {{&dmean, pm}, {&dcov, pm * q}, {&dgm, pm}, {&dgc, pm * q}, {&dparts, (size_t)P * md}})) return rc;
+  if (not_pd) HIPCHK(h, h->d_info.reserve(sizeof(int)));
+  JointScratch w[EHVI_MAX_P];
+  bool shared[EHVI_MAX_P];   // the member is this handle a second time: its arrays are overwritten between the two halves
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    shared[j] = false;
+    for (int i = 0; i < P; ++i) shared[j] = shared[j] || (i != j && hs[i] == t);
+    const size_t np = (size_t)t->Npad * Ppad;
+    const size_t part = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, t->dp));
+    w[j] = JointScratch{};
+    if (int rc = member_rc(h, t, carve(t, t->s_grad, {{&w[j].B, np}, {&w[j].C1, np}, {&w[j].T, np}, {&w[j].Z, np},
+                                                      {&w[j].S, gram ? (size_t)Ppad * Ppad : 0}, {&w[j].part, part}})))
+      return rc;
+  }
+  // `from`'s stream so far happens before whatever `to`'s stream is given next
+  auto order = [&](tgp_handle from, tgp_handle to) -> int {
+    if (from->stream == to->stream) return TGP_OK;
+    HIPCHK(h, hipEventRecord(from->ev_order, from->stream));
+    HIPCHK(h, hipStreamWaitEvent(to->stream, from->ev_order, 0));
+    return TGP_OK;
+  };
+  if (not_pd) HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    if (int rc = order(h, t)) return rc;   // the staged points
+    if (int rc = member_rc(h, t, forward(j, t, w[j], dmean + (size_t)j * M, dcov + (size_t)j * M * q))) return rc;
+    if (int rc = order(t, h)) return rc;
+  }
+  if (int rc = tail(dmean, dcov, dval, dgm, dgc)) return rc;
+  for (int j = 0; j < P; ++j) {
+    tgp_handle t = hs[j];
+    if (int rc = order(h, t)) return rc;   // the adjoints
+    if (shared[j])
+      if (int rc = member_rc(h, t, kstar_products(t, model_dev(t), t->d_W.as<double>(), t->Npad, dXq, M, Ppad, w[j].B, w[j].C1)))
+        return rc;
+    if (int rc = member_rc(h, t, joint_backward(t, w[j], dXq, M, Ppad, q, dgm + (size_t)j * M, dgc + (size_t)j * M * q,
+                                                dparts + (size_t)j * md)))
+      return rc;
+    if (int rc = order(t, h)) return rc;
+  }
+  launch_ehvi_sum_parts(h->stream, dparts, P, (int64_t)md, dgrad);
+  if (int rc = stage_out_finish(h, dval, val, (size_t)G, where)) return rc;
+  if (int rc = stage_out_finish(h, dgrad, grad, md, where)) return rc;
+  if (int rc = not_pd ? sync(h) : finish(h)) return rc;
+  ehvi_read_tail_ms(h);
+  h->ehvi_sweep_ms = 0.0;
+  h->last_ms = 0.0;
+  h->last_launches = P;
+  return not_pd ? info_finish(h, not_pd) : TGP_OK;
 }
 
 }  // namespace
@@ -3388,10 +3477,8 @@ int tgp_ehvi_moments_grad(tgp_handle h, const double* mean, const double* var, i
   return TGP_OK;
 }
 
-// Per member, on the member's own stream: K*^T and W K* (kstar_products) and the small-predict tail into the leading handle's
-// stacked moments; on the leading stream the gradient tail; per member again the posterior's vector-Jacobian product at q = 1
-// (joint_backward) on the SAME K*^T and W K* with (gmean_j, gvar_j) as adjoints; on the leading stream the sum over the
-// members.  The streams are ordered by each handle's ev_order; the one host synchronisation is the leading stream's.
+// stack_value_grad at q = 1: the forward half is K*^T and W K* (kstar_products) and the small-predict tail into mean and var --
+// not joint_forward, whose Gram product a marginal variance does not need.
 int tgp_ehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t M, double* val, double* grad, int where) {
   if (!hs || !hs[0]) return TGP_ERR_ARG;
   tgp_handle h = hs[0];
@@ -3400,71 +3487,19 @@ int tgp_ehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t M
   if (!Xq || !val || !grad) return fail(h, TGP_ERR_ARG, "Xq / val / grad is NULL");
   if (int rc = ehvi_check_stack(hs, P)) return rc;
   if (int rc = set_device(h)) return rc;
-  const int d = h->d;
   const int64_t Ppad = ((M + 63) / 64) * 64;
-  const size_t pm = (size_t)P * M, md = (size_t)M * d;
-  // every reservation first: a buffer that grows frees its old memory, which no stream may still be using
   const double* dXq;
-  double *dval, *dgrad, *dmean, *dvar, *dgm, *dgv, *dparts;
-  if (int rc = stage_in(h, h->s_in, Xq, md, where, &dXq)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)M, where, &dval)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out2, grad, md, where, &dgrad)) return rc;
-  if (int rc = carve(h, h->s_ehvi, {{&dmean, pm}, {&dvar, pm}, {&dgm, pm}, {&dgv, pm}, {&dparts, (size_t)P * md}})) return rc;
-  JointScratch w[EHVI_MAX_P];
-  bool shared[EHVI_MAX_P];   // the member is this handle a second time: its arrays are overwritten between the two halves
-  for (int j = 0; j < P; ++j) {
-    tgp_handle t = hs[j];
-    shared[j] = false;
-    for (int i = 0; i < P; ++i) shared[j] = shared[j] || (i != j && hs[i] == t);
-    const size_t np = (size_t)t->Npad * Ppad;
-    const size_t part = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, t->dp));
-    w[j] = JointScratch{};
-    if (int rc = carve(t, t->s_grad, {{&w[j].B, np}, {&w[j].C1, np}, {&w[j].T, np}, {&w[j].Z, np}, {&w[j].part, part}})) {
-      if (t != h) h->err = t->err;
-      return rc;
-    }
-  }
-  auto member = [&](tgp_handle t, int rc) {   // errors are reported on the leading handle
-    if (rc && t != h) h->err = t->err;
-    return rc;
-  };
-  // `from`'s stream so far happens before whatever `to`'s stream is given next
-  auto order = [&](tgp_handle from, tgp_handle to) -> int {
-    if (from->stream == to->stream) return TGP_OK;
-    HIPCHK(h, hipEventRecord(from->ev_order, from->stream));
-    HIPCHK(h, hipStreamWaitEvent(to->stream, from->ev_order, 0));
-    return TGP_OK;
-  };
-  auto products = [&](int j) {
-    return kstar_products(hs[j], model_dev(hs[j]), hs[j]->d_W.as<double>(), hs[j]->Npad, dXq, M, Ppad, w[j].B, w[j].C1);
-  };
-  for (int j = 0; j < P; ++j) {
-    tgp_handle t = hs[j];
-    if (int rc = order(h, t)) return rc;   // the staged candidates
-    if (int rc = member(t, products(j))) return rc;
-    launch_predict_small_tail(t->stream, model_dev(t), M, Ppad, w[j].B, w[j].C1, w[j].part, dmean + (size_t)j * M,
-                              dvar + (size_t)j * M);
-    if (int rc = order(t, h)) return rc;
-  }
-  if (int rc = ehvi_enqueue_grad_tail(h, dmean, dvar, M, 1, dval, dgm, dgv)) return rc;
-  for (int j = 0; j < P; ++j) {
-    tgp_handle t = hs[j];
-    if (int rc = order(h, t)) return rc;   // the adjoints
-    if (shared[j])
-      if (int rc = member(t, products(j))) return rc;
-    if (int rc = member(t, joint_backward(t, w[j], dXq, M, Ppad, 1, dgm + (size_t)j * M, dgv + (size_t)j * M, dparts + (size_t)j * md)))
-      return rc;
-    if (int rc = order(t, h)) return rc;
-  }
-  launch_ehvi_sum_parts(h->stream, dparts, P, (int64_t)md, dgrad);
-  if (int rc = stage_out_finish(h, dval, val, (size_t)M, where)) return rc;
-  if (int rc = stage_out_finish(h, dgrad, grad, md, where)) return rc;
-  if (int rc = finish(h)) return rc;
-  ehvi_read_tail_ms(h);
-  h->ehvi_sweep_ms = 0.0;
-  h->last_ms = 0.0;
-  h->last_launches = P;
-  return TGP_OK;
+  if (int rc = stage_in(h, h->s_in, Xq, (size_t)M * h->d, where, &dXq)) return rc;
+  return stack_value_grad(
+      hs, P, dXq, M, Ppad, 1, false, nullptr, val, grad, where,
+      [&](int, tgp_handle t, const JointScratch& w, double* dmean, double* dvar) {
+        if (int rc = kstar_products(t, model_dev(t), t->d_W.as<double>(), t->Npad, dXq, M, Ppad, w.B, w.C1)) return rc;
+        launch_predict_small_tail(t->stream, model_dev(t), M, Ppad, w.B, w.C1, w.part, dmean, dvar);
+        return (int)TGP_OK;
+      },
+      [&](const double* dmean, const double* dvar, double* dval, double* dgm, double* dgv) {
+        return ehvi_enqueue_grad_tail(h, dmean, dvar, M, 1, dval, dgm, dgv);
+      });
 }
 
 }  // extern "C"
@@ -3491,24 +3526,34 @@ int64_t qehvi_group_chunk(int P, int q) {
 // the tail on device-resident moments of `gc` groups (objective stride `gstride` groups), bracketed by the handle's events
 int qehvi_enqueue_tail(tgp_handle h, const double* dmean, const double* dcov, int64_t gc, int64_t gstride, int q,
                        const double* deps, int S, double jitter, double* dout) {
-  const double* db = h->d_ehvi.as<double>();
-  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  launch_qehvi_tail(h->stream, h->ehvi_P, h->ehvi_V, db, dc, h->ehvi_K, dmean, dcov, gc, gstride, q, deps, S, jitter, dout,
-                    h->d_info.as<int>());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  return TGP_OK;
+  const PartitionDev p = partition_dev(h);
+  return bracketed(h, [&] {
+    launch_qehvi_tail(h->stream, p.P, p.V, p.bounds, p.cells, p.K, dmean, dcov, gc, gstride, q, deps, S, jitter, dout,
+                      h->d_info.as<int>());
+  });
 }
 
 // the gradient tail likewise: dval [gc], dgm [P][gstride][q], dgc [P][gstride][q][q]
 int qehvi_enqueue_grad_tail(tgp_handle h, const double* dmean, const double* dcov, int64_t gc, int64_t gstride, int q,
                             const double* deps, int S, double jitter, int zero_clipped, double* dval, double* dgm, double* dgc) {
-  const double* db = h->d_ehvi.as<double>();
-  const uint32_t* dc = (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V);
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  launch_qehvi_grad_tail(h->stream, h->ehvi_P, h->ehvi_V, db, dc, h->ehvi_K, dmean, dcov, gc, gstride, q, deps, S, jitter,
-                         zero_clipped, dval, dgm, dgc, h->d_info.as<int>());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  const PartitionDev p = partition_dev(h);
+  return bracketed(h, [&] {
+    launch_qehvi_grad_tail(h->stream, p.P, p.V, p.bounds, p.cells, p.K, dmean, dcov, gc, gstride, q, deps, S, jitter, zero_clipped,
+                           dval, dgm, dgc, h->d_info.as<int>());
+  });
+}
+
+// host [P][G][n] -> buf [P][gc][n]: the groups g0 .. g0 + gc of every objective behind each other (enqueue only); and back
+int gather_stack_chunk(tgp_handle h, DevBuf& buf, const double* host, int P, int64_t G, int64_t g0, int64_t gc, int64_t n) {
+  for (int j = 0; j < P; ++j)
+    HIPCHK(h, hipMemcpyAsync(buf.as<double>() + (size_t)j * gc * n, host + ((int64_t)j * G + g0) * n,
+                             (size_t)gc * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  return TGP_OK;
+}
+int scatter_stack_chunk(tgp_handle h, double* host, const double* dev, int P, int64_t G, int64_t g0, int64_t gc, int64_t n) {
+  for (int j = 0; j < P; ++j)
+    HIPCHK(h, hipMemcpyAsync(host + ((int64_t)j * G + g0) * n, dev + (size_t)j * gc * n, (size_t)gc * n * sizeof(double),
+                             hipMemcpyDeviceToHost, h->stream));
   return TGP_OK;
 }
 
@@ -3535,12 +3580,8 @@ int tgp_qehvi_moments(tgp_handle h, const double* mean, const double* cov, int64
     if (where != TGP_DEVICE) {   // objective j's groups of this chunk behind each other: [P][gc]
       HIPCHK(h, h->s_out1.reserve((size_t)P * gc * q * sizeof(double)));
       HIPCHK(h, h->s_out2.reserve((size_t)P * gc * qq * sizeof(double)));
-      for (int j = 0; j < P; ++j) {
-        HIPCHK(h, hipMemcpyAsync(h->s_out1.as<double>() + (size_t)j * gc * q, mean + ((int64_t)j * G + g0) * q,
-                                 (size_t)gc * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->s_out2.as<double>() + (size_t)j * gc * qq, cov + ((int64_t)j * G + g0) * qq,
-                                 (size_t)gc * qq * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      }
+      if (int rb = gather_stack_chunk(h, h->s_out1, mean, P, G, g0, gc, q)) return rb;
+      if (int rb = gather_stack_chunk(h, h->s_out2, cov, P, G, g0, gc, qq)) return rb;
       dmean = h->s_out1.as<double>();
       dcov = h->s_out2.as<double>();
       gstride = gc;
@@ -3578,11 +3619,9 @@ int tgp_qehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t G, i
   const int rc = for_group_chunks(h, G, chunk, true, QEHVI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
     for (int j = 0; j < P; ++j) {
       // (tgp_predict_joint drains the member's stream before it returns: the tail below may run on the leading stream)
-      if (int rb = tgp_predict_joint(hs[j], dXq + g0 * q * d, gc, q, dmean + (size_t)j * gc * q, dcov + (size_t)j * gc * qq,
-                                     TGP_DEVICE)) {
-        if (hs[j] != h) h->err = hs[j]->err;
+      if (int rb = member_rc(h, hs[j], tgp_predict_joint(hs[j], dXq + g0 * q * d, gc, q, dmean + (size_t)j * gc * q,
+                                                         dcov + (size_t)j * gc * qq, TGP_DEVICE)))
         return rb;
-      }
       float ms = 0.f;   // both posterior paths leave the member's two events around their kernels
       if (hipEventElapsedTime(&ms, hs[j]->ev0, hs[j]->ev1) == hipSuccess) sweep_ms += ms;
       (void)hipGetLastError();
@@ -3599,7 +3638,7 @@ int tgp_qehvi_values(const tgp_handle* hs, int P, const double* Xq, int64_t G, i
   return rc;
 }
 
-// ---- the batch Monte-Carlo EHVI's gradient: qehvi_grad_tail_kernel on given moments, and tgp_ehvi_value_grad's body around it ------
+// ---- the batch Monte-Carlo EHVI's gradient: qehvi_grad_tail_kernel on given moments, and stack_value_grad around it -------------
 int tgp_qehvi_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
                            double jitter, double* val, double* gmean, double* gcov, int where) {
   if (!h) return TGP_ERR_ARG;
@@ -3625,12 +3664,8 @@ int tgp_qehvi_moments_grad(tgp_handle h, const double* mean, const double* cov, 
       HIPCHK(h, h->s_out2.reserve((size_t)P * gc * qq * sizeof(double)));
       HIPCHK(h, h->s_in.reserve((size_t)P * gc * q * sizeof(double)));
       HIPCHK(h, h->s_ent.reserve((size_t)P * gc * qq * sizeof(double)));
-      for (int j = 0; j < P; ++j) {
-        HIPCHK(h, hipMemcpyAsync(h->s_out1.as<double>() + (size_t)j * gc * q, mean + ((int64_t)j * G + g0) * q,
-                                 (size_t)gc * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->s_out2.as<double>() + (size_t)j * gc * qq, cov + ((int64_t)j * G + g0) * qq,
-                                 (size_t)gc * qq * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      }
+      if (int rb = gather_stack_chunk(h, h->s_out1, mean, P, G, g0, gc, q)) return rb;
+      if (int rb = gather_stack_chunk(h, h->s_out2, cov, P, G, g0, gc, qq)) return rb;
       dmean = h->s_out1.as<double>();
       dcov = h->s_out2.as<double>();
       dgm = h->s_in.as<double>();
@@ -3639,13 +3674,10 @@ int tgp_qehvi_moments_grad(tgp_handle h, const double* mean, const double* cov, 
     }
     if (int rb = stage_out_prepare(h, h->s_out3, val + g0, (size_t)gc, where, &dval)) return rb;
     if (int rb = qehvi_enqueue_grad_tail(h, dmean, dcov, gc, gstride, q, deps, S, jitter, 0, dval, dgm, dgc)) return rb;
-    if (where != TGP_DEVICE)
-      for (int j = 0; j < P; ++j) {
-        HIPCHK(h, hipMemcpyAsync(gmean + ((int64_t)j * G + g0) * q, dgm + (size_t)j * gc * q, (size_t)gc * q * sizeof(double),
-                                 hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(gcov + ((int64_t)j * G + g0) * qq, dgc + (size_t)j * gc * qq, (size_t)gc * qq * sizeof(double),
-                                 hipMemcpyDeviceToHost, h->stream));
-      }
+    if (where != TGP_DEVICE) {
+      if (int rb = scatter_stack_chunk(h, gmean, dgm, P, G, g0, gc, q)) return rb;
+      if (int rb = scatter_stack_chunk(h, gcov, dgc, P, G, g0, gc, qq)) return rb;
+    }
     return stage_out_finish(h, dval, val + g0, (size_t)gc, where);
   });
   h->ehvi_sweep_ms = 0.0;
@@ -3653,11 +3685,8 @@ int tgp_qehvi_moments_grad(tgp_handle h, const double* mean, const double* cov, 
   return rc;
 }
 
-// tgp_ehvi_value_grad at q > 1.  Per member, on the member's own stream: the forward half of the joint posterior (K*^T, W K*,
-// the Gram product, the small-predict tail, the pick kernel) into the leading handle's stacked moments; on the leading stream
-// the gradient tail; per member again the backward half (joint_backward) on the SAME K*^T and W K* with (gmean_j, gcov_j) as
-// adjoints; on the leading stream the sum over the members.  The streams are ordered by each handle's ev_order; the one host
-// synchronisation is the leading stream's.
+// stack_value_grad at q >= 1 with the joint posterior: the forward half is joint_forward (K*^T, W K*, the Gram product, the
+// small-predict tail, the pick kernel), the tail reports a breakdown through d_info.
 int tgp_qehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t G, int q, const double* eps, int S,
                          double jitter, double* val, double* grad, int where) {
   if (!hs || !hs[0]) return TGP_ERR_ARG;
@@ -3669,72 +3698,18 @@ int tgp_qehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t 
                 (long long)JOINT_SMALL_P);
   if (!Xq || !val || !grad) return fail(h, TGP_ERR_ARG, "Xq / val / grad is NULL");
   if (int rc = set_device(h)) return rc;
-  const int d = h->d;
   const int64_t M = G * (int64_t)q, Ppad = ((M + 63) / 64) * 64;
-  const size_t pm = (size_t)P * M, md = (size_t)M * d;
-  // every reservation first: a buffer that grows frees its old memory, which no stream may still be using
   const double *dXq, *deps;
-  double *dval, *dgrad, *dmean, *dcov, *dgm, *dgc, *dparts;
-  if (int rc = stage_in(h, h->s_in, Xq, md, where, &dXq)) return rc;
+  if (int rc = stage_in(h, h->s_in, Xq, (size_t)M * h->d, where, &dXq)) return rc;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)P * q * S, where, &deps)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out1, val, (size_t)G, where, &dval)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out2, grad, md, where, &dgrad)) return rc;
-  if (int rc = carve(h, h->s_ehvi, {{&dmean, pm}, {&dcov, pm * q}, {&dgm, pm}, {&dgc, pm * q}, {&dparts, (size_t)P * md}})) return rc;
-  HIPCHK(h, h->d_info.reserve(sizeof(int)));
-  JointScratch w[EHVI_MAX_P];
-  bool shared[EHVI_MAX_P];   // the member is this handle a second time: its arrays are overwritten between the two halves
-  for (int j = 0; j < P; ++j) {
-    tgp_handle t = hs[j];
-    shared[j] = false;
-    for (int i = 0; i < P; ++i) shared[j] = shared[j] || (i != j && hs[i] == t);
-    const size_t np = (size_t)t->Npad * Ppad;
-    const size_t part = std::max(predict_small_scratch_doubles(Ppad), grad_tail_scratch_doubles(Ppad, t->dp));
-    w[j] = JointScratch{};
-    if (int rc = carve(t, t->s_grad, {{&w[j].B, np}, {&w[j].C1, np}, {&w[j].T, np}, {&w[j].Z, np}, {&w[j].S, (size_t)Ppad * Ppad},
-                                      {&w[j].part, part}})) {
-      if (t != h) h->err = t->err;
-      return rc;
-    }
-  }
-  auto member = [&](tgp_handle t, int rc) {   // errors are reported on the leading handle
-    if (rc && t != h) h->err = t->err;
-    return rc;
-  };
-  // `from`'s stream so far happens before whatever `to`'s stream is given next
-  auto order = [&](tgp_handle from, tgp_handle to) -> int {
-    if (from->stream == to->stream) return TGP_OK;
-    HIPCHK(h, hipEventRecord(from->ev_order, from->stream));
-    HIPCHK(h, hipStreamWaitEvent(to->stream, from->ev_order, 0));
-    return TGP_OK;
-  };
-  HIPCHK(h, hipMemsetAsync(h->d_info.p, 0, sizeof(int), h->stream));
-  for (int j = 0; j < P; ++j) {
-    tgp_handle t = hs[j];
-    if (int rc = order(h, t)) return rc;   // the staged points
-    if (int rc = member(t, joint_forward(t, w[j], dXq, M, Ppad, q, dmean + (size_t)j * M, dcov + (size_t)j * M * q))) return rc;
-    if (int rc = order(t, h)) return rc;
-  }
-  if (int rc = qehvi_enqueue_grad_tail(h, dmean, dcov, G, G, q, deps, S, jitter, 1, dval, dgm, dgc)) return rc;
-  for (int j = 0; j < P; ++j) {
-    tgp_handle t = hs[j];
-    if (int rc = order(h, t)) return rc;   // the adjoints
-    if (shared[j])
-      if (int rc = member(t, kstar_products(t, model_dev(t), t->d_W.as<double>(), t->Npad, dXq, M, Ppad, w[j].B, w[j].C1)))
-        return rc;
-    if (int rc = member(t, joint_backward(t, w[j], dXq, M, Ppad, q, dgm + (size_t)j * M, dgc + (size_t)j * M * q,
-                                          dparts + (size_t)j * md)))
-      return rc;
-    if (int rc = order(t, h)) return rc;
-  }
-  launch_ehvi_sum_parts(h->stream, dparts, P, (int64_t)md, dgrad);
-  if (int rc = stage_out_finish(h, dval, val, (size_t)G, where)) return rc;
-  if (int rc = stage_out_finish(h, dgrad, grad, md, where)) return rc;
-  if (int rc = sync(h)) return rc;
-  ehvi_read_tail_ms(h);
-  h->ehvi_sweep_ms = 0.0;
-  h->last_ms = 0.0;
-  h->last_launches = P;
-  return info_finish(h, QEHVI_NOT_PD);
+  return stack_value_grad(
+      hs, P, dXq, M, Ppad, q, true, QEHVI_NOT_PD, val, grad, where,
+      [&](int, tgp_handle t, const JointScratch& w, double* dmean, double* dcov) {
+        return joint_forward(t, w, dXq, M, Ppad, q, dmean, dcov);
+      },
+      [&](const double* dmean, const double* dcov, double* dval, double* dgm, double* dgc) {
+        return qehvi_enqueue_grad_tail(h, dmean, dcov, G, G, q, deps, S, jitter, 1, dval, dgm, dgc);
+      });
 }
 
 int tgp_ehvi_last_ms(tgp_handle h, double* sweeps_ms, double* tail_ms) {

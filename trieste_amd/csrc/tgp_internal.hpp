@@ -300,6 +300,19 @@ void launch_bei_grad_tail(hipStream_t s, const double* mean, const double* cov, 
 // (row j ascending, nb[j] valid entries; nb is a HOST array), cells [K][P] packed words lower index | upper index << 16
 constexpr int EHVI_MAX_P = 4, EHVI_MAX_BOUNDS = 512;
 constexpr int64_t EHVI_MAX_CELLS = (int64_t)1 << 21;
+// The one step from a run-time number of objectives to an instantiation, in the spirit of with_dp:
+// f(std::integral_constant<int, P>{}) for P = 2 .. EHVI_MAX_P; the result is f's.  tgp_set_ehvi_partition admits no other P; one
+// that gets here all the same takes the last instantiation.
+template <int I = 2, typename F>
+inline auto with_objectives(int P, F&& f) {
+  static_assert(2 <= I && I <= EHVI_MAX_P, "the tails are instantiated for 2 .. EHVI_MAX_P objectives");
+  if constexpr (I < EHVI_MAX_P) {
+    if (P == I) return f(std::integral_constant<int, I>{});
+    return with_objectives<I + 1>(P, f);
+  } else {
+    return f(std::integral_constant<int, EHVI_MAX_P>{});
+  }
+}
 int ehvi_tile_width(int P, int V);   // candidates per workgroup: the largest power of two <= 64 with 8 P V C <= 160 KiB
 size_t ehvi_lds_bytes(int P, int V);
 void launch_ehvi_tail(hipStream_t s, int P, int V, const int* nb, const double* bounds, const uint32_t* cells, int K,

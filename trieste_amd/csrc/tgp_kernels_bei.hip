@@ -4,6 +4,7 @@
 //   (function/utils.py:29-199).
 #include "tgp_dev.hpp"
 #include "tgp_internal.hpp"
+#include "tgp_tail_dev.hpp"
 
 namespace tgp {
 
@@ -61,8 +62,8 @@ __device__ __forceinline__ double normal_quantile_mid(double p) {
 //   value = sum_i [(mu_i - T) p_i + sum_k Sigma^(i)_ki N(b_ik; m_ik, Sigma^(i)_kk) Phi_ik]            (:1724-1745)
 // on mu = -mean, T = -eta, cov + 1e-6 I (:1772-1803: the constant is the reference's own, not the builder's jitter).
 // A problem: the wave builds its n x n matrix (+ the CDF's own 1e-6 I, utils.py:143-144) row per lane in LDS and
-// factorises it as qei_tail_kernel does (pivot and multiplier through v_readlane, no barrier); then every lane walks
-// the chain of its sample (utils.py:166-197): y_0..y_{n-2} in registers (loops unrolled to QP), C_ij as LDS broadcast
+// factorises it with wave_chol_rows, as qei_tail_kernel does (pivot and multiplier through v_readlane, no barrier); then every
+// lane walks the chain of its sample (utils.py:166-197): y_0..y_{n-2} in registers (loops unrolled to QP), C_ij as LDS broadcast
 // reads, one Phi and one Phi^-1 per step.  Sums: per lane over its samples in order, xor-butterfly over the wave, the
 // q + q^2 terms by one thread in index order -- the same bits from every call.  No clip at zero (the estimate may be
 // slightly negative; the reference returns it as it is).
@@ -92,11 +93,6 @@ __global__ __launch_bounds__(64 * BEI_WAVES) void bei_tail_kernel(const double* 
   if ((int)threadIdx.x < q) mu[threadIdx.x] = -mean[g * q + threadIdx.x];
   __syncthreads();
   const double T = -eta;
-  auto bcast = [](double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-  };
   // Sigma^(i)_jk (function.py:1413-1424) and d_j = b_ij - m_ij (:1343-1352, :1480)
   auto sig = [&](int i, int j, int k) {
     const double a = (j != i && k != i) ? cv[j * q + k] : 0.0;
@@ -130,27 +126,12 @@ __global__ __launch_bounds__(64 * BEI_WAVES) void bei_tail_kernel(const double* 
         xs[lane] = dif(i, u) - dif(i, k) * (sku / skk);
       }
     }
-    for (int j = 0; j < n; ++j) {  // the factorisation of qei_tail_kernel
-      const double x = Lrow[j];
-      double dj = bcast(x, j);
-      if (!(dj > 0.0)) {
-        if (lane == 0) atomicCAS(info, 0, (int)(g % 2000000000) + 1);
-        dj = 1.0;
-      }
-      const double sd = sqrt(dj);
-      const double lij = lane == j ? sd : x / sd;
-      const bool below = live && lane > j;
-      if (live && lane >= j) Lrow[j] = lij;
-      const double nl = -lij;
-      for (int c = j + 1; c < n; ++c) {
-        const double lcj = bcast(lij, c);
-        if (below) Lrow[c] = fma(nl, lcj, Lrow[c]);
-      }
+    wave_chol_rows(Lrow, live, lane, n, g, info, [&](int j, double sd) {
       if (lane == j) {
         dg[j] = sd + 1e-12;  // utils.py:168, :183
         ig[j] = 1.0 / (sd + 1e-12);
       }
-    }
+    });
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // from here on every lane reads every row
     // t / dg[j]: the reciprocal is wave-uniform, one residual step gives the quotient's last bit
     auto over = [&](double t, int j) {
@@ -223,15 +204,15 @@ void launch_bei_tail(hipStream_t s, const double* mean, const double* cov, int64
 }
 
 // ---------------------------------------------------------------------------------------------
-// The value AND its adjoints w.r.t. (mean, cov): the forward tail above, problem for problem and operation for operation
-// (same build, factorisation, chain, sums), and behind every problem its reverse pass, all inside the wave that owns it:
+// The value AND its adjoints w.r.t. (mean, cov): the forward tail above, problem for problem (the same wave_chol_rows; same
+// build, chain, sums), and behind every problem its reverse pass, all inside the wave that owns it:
 //   chain     per sample, steps n-1 .. 0: e_r's adjoint = (prefix product)(suffix product) + ybar_r (1 - 2e-6) w_r / phi(y_r)
 //             [(Phi^-1)' = 1 / phi(y)], t_r's = ebar_r phi(t_r), through t_r = (x_r - sum_c C_rc y_c) / (C_rr + 1e-12) to xbar_r,
 //             Cbar_rc, Cbar_rr and ybar_c.  Prefix products, not f / e_r: an e_r may underflow to zero.
 //   sums      xbar [n] and Cbar [n (n + 1) / 2] over the samples.  QP <= 8: per-lane accumulators (the lane's samples in order),
 //             one butterfly per entry and problem.  QP = 16: 136 + 16 accumulators (304 registers) next to the chain's 80 doubles of
 //             state do not fit the register file, so every entry is reduced over the wave per 64-sample chunk and lane 0 adds the chunks in order.
-//   factor    Abar = C^-T sym(Phi(C^T Cbar)) C^-1, the in-wave form of qei_grad_tail_kernel (lane c owns column c / row c).
+//   factor    Abar = C^-T sym(Phi(C^T Cbar)) C^-1: chol_adjoint, as in qei_grad_tail_kernel (lane c owns column c / row c).
 //   problem   back through R^(i,k) = Sigma_uv - Sigma_ku Sigma_kv / Sigma_kk, c^(i,k) = d_u - d_k Sigma_ku / Sigma_kk and the
 //             weight Sigma_ki N(d_k; 0, Sigma_kk) (or mu_i - T) to the adjoints of Sigma^(i) [q][q] and d^(i) [q], and from
 //             there (rows by lane, row and column sums) into THIS WAVE's accumulators of cov's and mu's adjoints.
@@ -276,11 +257,6 @@ __global__ __launch_bounds__(64 * BEI_WAVES) void bei_grad_tail_kernel(const dou
   for (int t = lane; t < q * q + q; t += 64) cvb[t] = 0.0;   // (cvb and mub are contiguous)
   __syncthreads();
   const double T = -eta;
-  auto bcast = [](double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-  };
   auto sig = [&](int i, int j, int k) {
     const double a = (j != i && k != i) ? cv[j * q + k] : 0.0;
     const double b = j != i ? cv[j * q + i] : 0.0;
@@ -318,27 +294,12 @@ __global__ __launch_bounds__(64 * BEI_WAVES) void bei_grad_tail_kernel(const dou
       for (int c = 0; c < n; ++c) Mrow[c] = 0.0;
       xb[lane] = 0.0;
     }
-    for (int j = 0; j < n; ++j) {  // the factorisation of bei_tail_kernel
-      const double x = Lrow[j];
-      double dj = bcast(x, j);
-      if (!(dj > 0.0)) {
-        if (lane == 0) atomicCAS(info, 0, (int)(g % 2000000000) + 1);
-        dj = 1.0;
-      }
-      const double sd = sqrt(dj);
-      const double lij = lane == j ? sd : x / sd;
-      const bool below = live && lane > j;
-      if (live && lane >= j) Lrow[j] = lij;
-      const double nl = -lij;
-      for (int c = j + 1; c < n; ++c) {
-        const double lcj = bcast(lij, c);
-        if (below) Lrow[c] = fma(nl, lcj, Lrow[c]);
-      }
+    wave_chol_rows(Lrow, live, lane, n, g, info, [&](int j, double sd) {
       if (lane == j) {
         dg[j] = sd + 1e-12;
         ig[j] = 1.0 / (sd + 1e-12);
       }
-    }
+    });
     wfence();
     auto over = [&](double t, int j) {
       const double z = t * ig[j];
@@ -457,29 +418,7 @@ __global__ __launch_bounds__(64 * BEI_WAVES) void bei_grad_tail_kernel(const dou
     }
     wfence();
     // the factor's adjoint, lane = column: Q = tril(C^T Cbar) / 2 in place, mirrored, C^-T from the left, C^-1 from the right
-    if (live)
-      for (int a = lane; a < n; ++a) {
-        double t = 0.0;
-        for (int c = a; c < n; ++c) t = fma(Ls[c * ldq + a], Ms[c * ldq + lane], t);
-        Ms[a * ldq + lane] = 0.5 * t;
-      }
-    wfence();
-    if (live)
-      for (int a = 0; a < lane; ++a) Ms[a * ldq + lane] = Ms[lane * ldq + a];
-    wfence();
-    if (live)
-      for (int a = n - 1; a >= 0; --a) {
-        double t = Ms[a * ldq + lane];
-        for (int c = a + 1; c < n; ++c) t = fma(-Ls[c * ldq + a], Ms[c * ldq + lane], t);
-        Ms[a * ldq + lane] = t / Ls[a * ldq + a];
-      }
-    wfence();
-    if (live)
-      for (int a = n - 1; a >= 0; --a) {
-        double t = Mrow[a];
-        for (int c = a + 1; c < n; ++c) t = fma(-Ls[c * ldq + a], Mrow[c], t);
-        Mrow[a] = t / Ls[a * ldq + a];
-      }
+    chol_adjoint(Ls, Ms, ldq, n, lane, live, wfence);
     wfence();
     // back through the problem's construction to the adjoints of Sigma^(i) (Sp) and d^(i) (dp)
     const double* Sp = Ms;

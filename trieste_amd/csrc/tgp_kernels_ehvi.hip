@@ -148,18 +148,28 @@ __global__ __launch_bounds__(EHVI_THREADS) void ehvi_tail_kernel(const double* _
   }
 }
 
+// what both launchers derive from the tile width C (a power of two): its logarithm, the grid, the bound counts by value
+struct EhviTile {
+  int logC = 0;
+  EhviDims dims{};
+  int64_t grid = 0;
+};
+static EhviTile ehvi_tile(int P, int C, const int* nb, int64_t M) {
+  EhviTile t;
+  while ((1 << t.logC) < C) ++t.logC;
+  for (int j = 0; j < P; ++j) t.dims.nb[j] = nb[j];
+  t.grid = (M + C - 1) / C;
+  return t;
+}
+
 template <int P>
 void launch_ehvi_p(hipStream_t s, int V, const int* nb, const double* bounds, const uint32_t* cells, int K, const double* mean,
                    const double* var, int64_t M, double* out) {
   (void)hipFuncSetAttribute((const void*)ehvi_tail_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, EHVI_LDS);
   const int C = ehvi_tile_width(P, V);
-  int logC = 0;
-  while ((1 << logC) < C) ++logC;
-  EhviDims dims{};
-  for (int j = 0; j < P; ++j) dims.nb[j] = nb[j];
-  const int64_t grid = (M + C - 1) / C;
-  hipLaunchKernelGGL(ehvi_tail_kernel<P>, dim3((unsigned)grid), dim3(EHVI_THREADS), ehvi_lds_bytes(P, V), s, mean, var, M, bounds,
-                     dims, V, cells, K, logC, out);
+  const EhviTile t = ehvi_tile(P, C, nb, M);
+  hipLaunchKernelGGL(ehvi_tail_kernel<P>, dim3((unsigned)t.grid), dim3(EHVI_THREADS), ehvi_lds_bytes(P, V), s, mean, var, M, bounds,
+                     t.dims, V, cells, K, t.logC, out);
 }
 
 // ---- the value with the adjoints of the moments: what an L-BFGS-B iteration over EHVI asks for -------------------
@@ -292,13 +302,9 @@ void launch_ehvi_grad_p(hipStream_t s, int V, const int* nb, const double* bound
                         double* gvar) {
   (void)hipFuncSetAttribute((const void*)ehvi_grad_tail_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, EHVI_LDS);
   const int C = ehvi_grad_tile_width(P, V);
-  int logC = 0;
-  while ((1 << logC) < C) ++logC;
-  EhviDims dims{};
-  for (int j = 0; j < P; ++j) dims.nb[j] = nb[j];
-  const int64_t grid = (M + C - 1) / C;
-  hipLaunchKernelGGL(ehvi_grad_tail_kernel<P>, dim3((unsigned)grid), dim3(EHVI_THREADS), ehvi_grad_lds_bytes(P, V), s, mean, var, M,
-                     bounds, dims, V, cells, K, logC, zero_clipped, val, gmean, gvar);
+  const EhviTile t = ehvi_tile(P, C, nb, M);
+  hipLaunchKernelGGL(ehvi_grad_tail_kernel<P>, dim3((unsigned)t.grid), dim3(EHVI_THREADS), ehvi_grad_lds_bytes(P, V), s, mean, var, M,
+                     bounds, t.dims, V, cells, K, t.logC, zero_clipped, val, gmean, gvar);
 }
 
 // out [n] = ((part_0 + part_1) + part_2) + part_3 over the first P of the arrays part_j = parts + j n: one fixed association
@@ -327,9 +333,9 @@ void launch_ehvi_grad_tail(hipStream_t s, int P, int V, const int* nb, const dou
                            const double* mean, const double* var, int64_t M, int zero_clipped, double* val, double* gmean,
                            double* gvar) {
   if (M <= 0) return;
-  if (P == 2) launch_ehvi_grad_p<2>(s, V, nb, bounds, cells, K, mean, var, M, zero_clipped, val, gmean, gvar);
-  else if (P == 3) launch_ehvi_grad_p<3>(s, V, nb, bounds, cells, K, mean, var, M, zero_clipped, val, gmean, gvar);
-  else launch_ehvi_grad_p<4>(s, V, nb, bounds, cells, K, mean, var, M, zero_clipped, val, gmean, gvar);
+  with_objectives(P, [&](auto PC) {
+    launch_ehvi_grad_p<decltype(PC)::value>(s, V, nb, bounds, cells, K, mean, var, M, zero_clipped, val, gmean, gvar);
+  });
 }
 
 void launch_ehvi_sum_parts(hipStream_t s, const double* parts, int P, int64_t n, double* out) {
@@ -351,9 +357,7 @@ size_t ehvi_lds_bytes(int P, int V) {
 void launch_ehvi_tail(hipStream_t s, int P, int V, const int* nb, const double* bounds, const uint32_t* cells, int K,
                       const double* mean, const double* var, int64_t M, double* out) {
   if (M <= 0) return;
-  if (P == 2) launch_ehvi_p<2>(s, V, nb, bounds, cells, K, mean, var, M, out);
-  else if (P == 3) launch_ehvi_p<3>(s, V, nb, bounds, cells, K, mean, var, M, out);
-  else launch_ehvi_p<4>(s, V, nb, bounds, cells, K, mean, var, M, out);
+  with_objectives(P, [&](auto PC) { launch_ehvi_p<decltype(PC)::value>(s, V, nb, bounds, cells, K, mean, var, M, out); });
 }
 
 }  // namespace tgp

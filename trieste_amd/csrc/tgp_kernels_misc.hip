@@ -3,6 +3,7 @@
 // evaluation.
 #include "tgp_dev.hpp"
 #include "tgp_internal.hpp"
+#include "tgp_tail_dev.hpp"
 
 namespace tgp {
 
@@ -566,7 +567,7 @@ void launch_sample_box(hipStream_t s, uint64_t seed, int64_t first, int64_t M, i
 // == BatchReparametrizationSampler.sample (sampler.py:278-287) + batch_monte_carlo_expected_
 // improvement.__call__ (function.py:1183-1186).  (SURVEY K2 batched, K8.)
 // Round 2's form (one 256-thread workgroup per group, three barriers per pivot, eps re-read from L2 for every (j, k))
-// took 33 ms for C4's 10^5 groups, 7 % of the step; its arithmetic is kept operation for operation:
+// took 33 ms for C4's 10^5 groups, 7 % of the step; its arithmetic is kept (the factorisation is wave_chol_rows, tgp_tail_dev.hpp):
 //  * factorisation: lane i owns row i, kept in its own LDS row (odd row stride: conflict-free); the pivot and the
 //    multiplier l_kj reach every lane through v_readlane (-> a scalar operand of the FMA), so no lane ever reads
 //    another lane's LDS data: no barrier, no fence, and the compiler is free to pipeline the row updates.  Entries
@@ -587,11 +588,6 @@ __global__ __launch_bounds__(64, 2) void qei_tail_kernel(const double* __restric
   const int ldq = q | 1;  // odd row stride
   double* const Ls = qei_lds;       // [q][ldq] (+ QP of slack: the last row group reads, and drops, rows beyond q)
   double* const mu = qei_lds + q * ldq + QP;
-  auto bcast = [](double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-  };
   const bool live = lane < q;
   double* const Lrow = Ls + (live ? lane : 0) * ldq;
   if (live) {
@@ -599,23 +595,7 @@ __global__ __launch_bounds__(64, 2) void qei_tail_kernel(const double* __restric
     for (int k = 0; k < q; ++k) Lrow[k] = crow[k] + (k == lane ? jitter : 0.0);
     mu[lane] = mean[g * q + lane];
   }
-  for (int j = 0; j < q; ++j) {
-    const double x = Lrow[j];
-    double dj = bcast(x, j);
-    if (!(dj > 0.0)) {
-      if (lane == 0) atomicCAS(info, 0, (int)(g % 2000000000) + 1);
-      dj = 1.0;
-    }
-    const double sd = sqrt(dj);
-    const double lij = lane == j ? sd : x / sd;
-    const bool below = live && lane > j;
-    if (live && lane >= j) Lrow[j] = lij;
-    const double nl = -lij;
-    for (int k = j + 1; k < q; ++k) {
-      const double lkj = bcast(lij, k);
-      if (below) Lrow[k] = fma(nl, lkj, Lrow[k]);
-    }
-  }
+  wave_chol_rows(Lrow, live, lane, q, g, info, [](int, double) {});
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // from here on every lane reads every row
   constexpr int RG = 2;
   double acc = 0.0;
@@ -679,7 +659,8 @@ void launch_qei_tail(hipStream_t s, const double* mean, const double* cov, int64
 //   d value / d f_s,i = -1/S  where i is the (first) arg-min of an improving sample  ->  gmean_i = sum_s ...,  Lbar = tril(sum_s df_s eps_s^T)
 //   gcov = L^-T sym(Phi(L^T Lbar)) L^-1   (the Cholesky adjoint; Phi: lower triangle, diagonal halved), a clipped diagonal entry of
 //   cov (interface.py:129-131: tf.clip_by_value) gets zero.
-// Factorisation and samples as in qei_tail_kernel (same arithmetic, operation for operation: the value is tgp_qei's); every later
+// The factorisation is the helper that qei_tail_kernel calls, the sample loop its loop written out again -- as one shared
+// function it compiled to other register counts in both kernels -- (the value is tgp_qei's bit for bit); every later
 // phase gives lane c column c (or row r) of the q x q work matrix in LDS -- fixed summation orders, no atomics: bit-identical
 // run to run.  q x q arithmetic per group, 10 ... 300 groups per call: none of it is a roofline item.
 template <int QP>
@@ -696,11 +677,6 @@ __global__ __launch_bounds__(64) void qei_grad_tail_kernel(const double* __restr
   double* const Ms = Ls + q * ldq + QP;          // [q][ldq]: Lbar -> Q -> R -> L^-T R -> gcov, in place
   double* const mu = Ms + q * ldq;               // [QP]
   int* const jm = (int*)(mu + QP);               // [S]: arg-min row of an improving sample, -1 otherwise
-  auto bcast = [](double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-  };
   const bool live = lane < q;
   double* const Lrow = Ls + (live ? lane : 0) * ldq;
   bool clipped = false;
@@ -711,23 +687,7 @@ __global__ __launch_bounds__(64) void qei_grad_tail_kernel(const double* __restr
     mu[lane] = mean[g * q + lane];
     for (int i = 0; i < q; ++i) Ms[i * ldq + lane] = 0.0;
   }
-  for (int j = 0; j < q; ++j) {
-    const double x = Lrow[j];
-    double dj = bcast(x, j);
-    if (!(dj > 0.0)) {
-      if (lane == 0) atomicCAS(info, 0, (int)(g % 2000000000) + 1);
-      dj = 1.0;
-    }
-    const double sd = sqrt(dj);
-    const double lij = lane == j ? sd : x / sd;
-    const bool below = live && lane > j;
-    if (live && lane >= j) Lrow[j] = lij;
-    const double nl = -lij;
-    for (int k = j + 1; k < q; ++k) {
-      const double lkj = bcast(lij, k);
-      if (below) Lrow[k] = fma(nl, lkj, Lrow[k]);
-    }
-  }
+  wave_chol_rows(Lrow, live, lane, q, g, info, [](int, double) {});
   __syncthreads();
   constexpr int RG = 2;
   double acc = 0.0;
@@ -784,34 +744,10 @@ __global__ __launch_bounds__(64) void qei_grad_tail_kernel(const double* __restr
       if (i >= lane) Ms[i * ldq + lane] += ec[s];
     }
     gmean[g * q + lane] = ninv * (double)cnt;
-    // Q = tril(L^T Lbar) in place, column c: Q[a][c] = sum_{k >= a} L[k][a] Lbar[k][c]  (rows ascending: row a is read before it
-    // is written and never again), then R's lower triangle = Q / 2 (Phi halves the diagonal, sym the rest)
-    for (int a = lane; a < q; ++a) {
-      double t = 0.0;
-      for (int k = a; k < q; ++k) t = fma(Ls[k * ldq + a], ninv * Ms[k * ldq + lane], t);
-      Ms[a * ldq + lane] = 0.5 * t;
-    }
+    for (int k = lane; k < q; ++k) Ms[k * ldq + lane] *= ninv;  // Lbar's scale, on its lower triangle
   }
-  __syncthreads();
-  if (live)
-    for (int a = 0; a < lane; ++a) Ms[a * ldq + lane] = Ms[lane * ldq + a];  // R = R^T
-  __syncthreads();
-  if (live)  // Y = L^-T R: back substitution down column c
-    for (int a = q - 1; a >= 0; --a) {
-      double t = Ms[a * ldq + lane];
-      for (int k = a + 1; k < q; ++k) t = fma(-Ls[k * ldq + a], Ms[k * ldq + lane], t);
-      Ms[a * ldq + lane] = t / Ls[a * ldq + a];
-    }
-  __syncthreads();
-  if (live) {  // gcov = Y L^-1: back substitution along row r
-    double* const row = Ms + lane * ldq;
-    for (int a = q - 1; a >= 0; --a) {
-      double t = row[a];
-      for (int k = a + 1; k < q; ++k) t = fma(-Ls[k * ldq + a], row[k], t);
-      row[a] = t / Ls[a * ldq + a];
-    }
-    if (clipped) row[lane] = 0.0;
-  }
+  chol_adjoint(Ls, Ms, ldq, q, lane, live, [] { __syncthreads(); });
+  if (live && clipped) Ms[lane * ldq + lane] = 0.0;
   __syncthreads();
   if (live)
     for (int r = 0; r < q; ++r) gcov[(g * q + r) * q + lane] = Ms[r * ldq + lane];

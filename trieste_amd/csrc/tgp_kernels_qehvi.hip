@@ -28,6 +28,7 @@
 //   LDS          8 (P q C' + P q q + P q) bytes, C' = min(C, S rounded up to 64): at most 32 KiB + 2.3 KiB, 4 workgroups per CU
 #include "tgp_dev.hpp"
 #include "tgp_internal.hpp"
+#include "tgp_tail_dev.hpp"
 
 namespace tgp {
 
@@ -59,23 +60,13 @@ __device__ __forceinline__ void qehvi_walk(const double* Ys, int ldi, int ldj, c
   }
 }
 
+// phase 1: the moments of batch g into LDS (Ls [P][q][q] = cov + jitter I, mu [P][q]), then thread j < P factorises matrix j
+// in place.  A non-positive pivot reports the group (first report wins) and goes on with pivot 1.  Ends in a barrier.
 template <int P>
-__global__ __launch_bounds__(QEHVI_THREADS) void qehvi_tail_kernel(const double* __restrict__ mean,
-                                                                   const double* __restrict__ cov, int64_t gstride, int q,
-                                                                   const double* __restrict__ eps, int S, int chunk,
-                                                                   double jitter, const double* __restrict__ bounds, int V,
-                                                                   const uint32_t* __restrict__ cells, int K,
-                                                                   double* __restrict__ out, int* __restrict__ info) {
-  extern __shared__ double qehvi_lds[];
-  const int tid = (int)threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t g = blockIdx.x;
+__device__ __forceinline__ void qehvi_load_and_factor(const double* __restrict__ mean, const double* __restrict__ cov,
+                                                      int64_t gstride, int64_t g, int q, double jitter, double* Ls, double* mu,
+                                                      int* info, int tid) {
   const int qq = q * q;
-  double* const Ls = qehvi_lds;        // [P][q][q]
-  double* const mu = Ls + P * qq;      // [P][q]
-  double* const Y = mu + P * q;        // [P][q][chunk]; afterwards [4][64] partial sums
-
-  // phase 1: moments in, P factorisations
   for (int e = tid; e < P * qq; e += QEHVI_THREADS) {
     const int j = e / qq, r = e - j * qq, i = r / q, k = r - i * q;
     Ls[e] = cov[((int64_t)j * gstride + g) * qq + r] + (i == k ? jitter : 0.0);
@@ -103,24 +94,77 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_tail_kernel(const double*
     }
   }
   __syncthreads();
+}
+
+// phase 2: the cs samples from s0 on into Y [P][q][ld] (sample index fastest, the pad zero), one thread per entry: the fma
+// chain from the mean over m = 0..i.  The caller synchronises.
+template <int P>
+__device__ __forceinline__ void qehvi_fill_samples(const double* Ls, const double* mu, const double* __restrict__ eps, int q,
+                                                   int S, int s0, int cs, int ld, double* Y, int tid) {
+  const int qq = q * q;
+  for (int e = tid; e < P * q * ld; e += QEHVI_THREADS) {
+    const int ji = e / ld, s = e - ji * ld;
+    const int j = ji / q, i = ji - j * q;
+    double y = 0.0;
+    if (s < cs) {
+      y = mu[ji];
+      const double* const Lr = Ls + j * qq + i * q;
+      const double* const ep = eps + (int64_t)j * q * S + s0 + s;
+      for (int m2 = 0; m2 <= i; ++m2) y = fma(Lr[m2], ep[(int64_t)m2 * S], y);
+    }
+    Y[e] = y;
+  }
+}
+
+// cell k's bounds (wave-uniform: scalar loads; a lower bound below -1e10 is taken as -1e10) and the walk's starting minima
+template <int P>
+__device__ __forceinline__ void qehvi_cell_bounds(const double* __restrict__ bounds, int V, const uint32_t* __restrict__ cells,
+                                                  int k, double (&lb)[P], double (&ub)[P], double (&top)[P]) {
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const uint32_t w = cells[(size_t)k * P + j];
+    lb[j] = fmax(bounds[j * V + (int)(w & 0xffffu)], -1e10);
+    ub[j] = bounds[j * V + (int)(w >> 16)];
+    top[j] = INFINITY;
+  }
+}
+
+// the value from every thread's acc through Y [slice][lane] (one barrier): the four slices of a lane in slice order, the fixed
+// butterfly over the 64 lanes, one division by S
+__device__ __forceinline__ void qehvi_reduce_value(double* Y, double acc, int tid, int S, double* out) {
+  Y[tid] = acc;
+  __syncthreads();
+  if (tid < 64) {
+    double sum = Y[tid];
+    for (int w = 1; w < QEHVI_WAVES; ++w) sum += Y[w * 64 + tid];
+    sum = wave_sum(sum);
+    if (tid == 0) *out = sum / (double)S;
+  }
+}
+
+template <int P>
+__global__ __launch_bounds__(QEHVI_THREADS) void qehvi_tail_kernel(const double* __restrict__ mean,
+                                                                   const double* __restrict__ cov, int64_t gstride, int q,
+                                                                   const double* __restrict__ eps, int S, int chunk,
+                                                                   double jitter, const double* __restrict__ bounds, int V,
+                                                                   const uint32_t* __restrict__ cells, int K,
+                                                                   double* __restrict__ out, int* __restrict__ info) {
+  extern __shared__ double qehvi_lds[];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t g = blockIdx.x;
+  const int qq = q * q;
+  double* const Ls = qehvi_lds;        // [P][q][q]
+  double* const mu = Ls + P * qq;      // [P][q]
+  double* const Y = mu + P * q;        // [P][q][chunk]; afterwards [4][64] partial sums
+
+  qehvi_load_and_factor<P>(mean, cov, gstride, g, q, jitter, Ls, mu, info, tid);
 
   double acc = 0.0;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cs = min(chunk, S - s0);       // samples of this chunk
     const int ld = (cs + 63) & ~63;          // row length in LDS (<= the allocation's)
-    // phase 2: the chunk's samples
-    for (int e = tid; e < P * q * ld; e += QEHVI_THREADS) {
-      const int ji = e / ld, s = e - ji * ld;
-      const int j = ji / q, i = ji - j * q;
-      double y = 0.0;
-      if (s < cs) {
-        y = mu[ji];
-        const double* const Lr = Ls + j * qq + i * q;
-        const double* const ep = eps + (int64_t)j * q * S + s0 + s;
-        for (int m2 = 0; m2 <= i; ++m2) y = fma(Lr[m2], ep[(int64_t)m2 * S], y);
-      }
-      Y[e] = y;
-    }
+    qehvi_fill_samples<P>(Ls, mu, eps, q, S, s0, cs, ld, Y, tid);
     __syncthreads();
     // phase 3: the cells of slice `wave` for the samples lane, lane + 64, ...
     for (int b = 0; b < ld; b += 64) {
@@ -128,13 +172,7 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_tail_kernel(const double*
       const double* const Ys = Y + b + lane;
       for (int k = wave; k < K; k += QEHVI_WAVES) {
         double lb[P], ub[P], top[P];
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const uint32_t w = cells[(size_t)k * P + j];
-          lb[j] = fmax(bounds[j * V + (int)(w & 0xffffu)], -1e10);
-          ub[j] = bounds[j * V + (int)(w >> 16)];
-          top[j] = INFINITY;
-        }
+        qehvi_cell_bounds<P>(bounds, V, cells, k, lb, ub, top);
         double c = 0.0;
         if (valid) qehvi_walk<P, 1>(Ys, ld, q * ld, lb, ub, top, 0, q, c);
         acc += c;
@@ -142,14 +180,7 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_tail_kernel(const double*
     }
     __syncthreads();
   }
-  Y[tid] = acc;   // [slice][lane]
-  __syncthreads();
-  if (tid < 64) {
-    double sum = Y[tid];
-    for (int w = 1; w < QEHVI_WAVES; ++w) sum += Y[w * 64 + tid];
-    sum = wave_sum(sum);
-    if (tid == 0) out[g] = sum / (double)S;
-  }
+  qehvi_reduce_value(Y, acc, tid, S, out + g);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -164,8 +195,8 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_tail_kernel(const double*
 //   gcov[j]                      L_j^-T sym(Phi(L_j^T Lbar_j)) L_j^-1 (qei_grad_tail_kernel's form); zero_clipped: a diagonal
 //                                entry of cov at VAR_FLOOR gets zero
 //
-// Phases 1 and 2 and the value's sums are qehvi_tail_kernel's, operation for operation: a lane adds its (64-block, cell) sums in
-// the same order whatever the chunk, so the smaller chunk here (qehvi_grad_sample_chunk) leaves the value's bits alone.
+// Phases 1 and 2, the cell bounds and the value's sums are the helpers that qehvi_tail_kernel calls: a lane adds its
+// (64-block, cell) sums in the same order whatever the chunk, so the smaller chunk here (qehvi_grad_sample_chunk) leaves the value's bits alone.
 //   phase 3      the walk also carries, per level and objective, WHICH level of the path owns the running minimum (0: nobody --
 //                the owner's sample sits at or below the cell's lower bound).  Every level has P accumulators in registers (the
 //                template recursion's frames: "the adjoint of the point at this level"); a live term adds its P partial
@@ -248,35 +279,8 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_grad_tail_kernel(
   double* const Y = Es + P * nent;     // [P][q][rowcap]; afterwards [4][64] partial sums
   double* const Yb = Y + P * q * rowcap;   // [4][P][q][rowcap]: one adjoint copy per wave
 
-  // phase 1: moments in, P factorisations (qehvi_tail_kernel's)
-  for (int e = tid; e < P * qq; e += QEHVI_THREADS) {
-    const int j = e / qq, r = e - j * qq, i = r / q, k = r - i * q;
-    Ls[e] = cov[((int64_t)j * gstride + g) * qq + r] + (i == k ? jitter : 0.0);
-  }
-  for (int e = tid; e < P * q; e += QEHVI_THREADS) {
-    const int j = e / q;
-    mu[e] = mean[((int64_t)j * gstride + g) * q + (e - j * q)];
-  }
   for (int e = tid; e < P * nent; e += QEHVI_THREADS) Es[e] = 0.0;
-  __syncthreads();
-  if (tid < P) {
-    double* const A = Ls + tid * qq;
-    for (int j = 0; j < q; ++j) {
-      double dj = A[j * q + j];
-      if (!(dj > 0.0)) {
-        atomicCAS(info, 0, (int)(g % 2000000000) + 1);
-        dj = 1.0;
-      }
-      const double sd = sqrt(dj);
-      A[j * q + j] = sd;
-      for (int i = j + 1; i < q; ++i) A[i * q + j] = A[i * q + j] / sd;
-      for (int i = j + 1; i < q; ++i) {
-        const double nl = -A[i * q + j];
-        for (int k = j + 1; k <= i; ++k) A[i * q + k] = fma(nl, A[k * q + j], A[i * q + k]);
-      }
-    }
-  }
-  __syncthreads();
+  qehvi_load_and_factor<P>(mean, cov, gstride, g, q, jitter, Ls, mu, info, tid);
 
   double acc = 0.0;
   QehviAdj<P> A;   // every level flushes and clears its own slots before its loop moves on: cleared once, here
@@ -289,18 +293,7 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_grad_tail_kernel(
     const int ld = (cs + 63) & ~63;          // row length in LDS (<= rowcap)
     const int pql = P * q * ld;
     // phase 2: the chunk's samples, the adjoint copies cleared
-    for (int e = tid; e < pql; e += QEHVI_THREADS) {
-      const int ji = e / ld, s = e - ji * ld;
-      const int j = ji / q, i = ji - j * q;
-      double y = 0.0;
-      if (s < cs) {
-        y = mu[ji];
-        const double* const Lr = Ls + j * qq + i * q;
-        const double* const ep = eps + (int64_t)j * q * S + s0 + s;
-        for (int m2 = 0; m2 <= i; ++m2) y = fma(Lr[m2], ep[(int64_t)m2 * S], y);
-      }
-      Y[e] = y;
-    }
+    qehvi_fill_samples<P>(Ls, mu, eps, q, S, s0, cs, ld, Y, tid);
     for (int e = tid; e < QEHVI_WAVES * pql; e += QEHVI_THREADS) Yb[e] = 0.0;
     __syncthreads();
     // phase 3: the cells of slice `wave` for the samples lane, lane + 64, ...
@@ -311,14 +304,9 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_grad_tail_kernel(
       for (int k = wave; k < K; k += QEHVI_WAVES) {
         double lb[P], ub[P], top[P];
         int nobody[P];
+        qehvi_cell_bounds<P>(bounds, V, cells, k, lb, ub, top);
 #pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const uint32_t w = cells[(size_t)k * P + j];
-          lb[j] = fmax(bounds[j * V + (int)(w & 0xffffu)], -1e10);
-          ub[j] = bounds[j * V + (int)(w >> 16)];
-          top[j] = INFINITY;
-          nobody[j] = 0;
-        }
+        for (int j = 0; j < P; ++j) nobody[j] = 0;
         double c = 0.0;
         if (valid) qehvi_walk_grad<P, 1>(Ys, Ybw + b + lane, ld, q * ld, lb, ub, top, nobody, 0, q, c, A);
         acc += c;
@@ -354,7 +342,6 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_grad_tail_kernel(
     }
     __syncthreads();
   }
-  Y[tid] = acc;   // [slice][lane]
   // Lbar's lower triangle into Ms, scaled; the means' adjoints out
   const double invS = 1.0 / (double)S;
   for (int e = tid; e < P * nent; e += QEHVI_THREADS) {
@@ -371,42 +358,12 @@ __global__ __launch_bounds__(QEHVI_THREADS) void qehvi_grad_tail_kernel(
       Ms[j * qq + i * q + t] = v;
     }
   }
-  __syncthreads();
-  if (tid < 64) {
-    double sum = Y[tid];
-    for (int w = 1; w < QEHVI_WAVES; ++w) sum += Y[w * 64 + tid];
-    sum = wave_sum(sum);
-    if (tid == 0) val[g] = sum / (double)S;
-  }
-  // phase 4b: wave j takes objective j (P <= 4 waves); lane c owns column c, later row c (qei_grad_tail_kernel's steps)
+  qehvi_reduce_value(Y, acc, tid, S, val + g);
+  // phase 4b: wave j takes objective j (P <= 4 waves); lane c owns column c, later row c (chol_adjoint, as in qei_grad_tail_kernel)
   const bool work = wave < P && lane < q;
   const double* const L = Ls + (wave < P ? wave : 0) * qq;
   double* const M = Ms + (wave < P ? wave : 0) * qq;
-  if (work)   // Q = tril(L^T Lbar) in place, rows ascending; R's lower triangle = Q / 2
-    for (int a = lane; a < q; ++a) {
-      double t = 0.0;
-      for (int k = a; k < q; ++k) t = fma(L[k * q + a], M[k * q + lane], t);
-      M[a * q + lane] = 0.5 * t;
-    }
-  __syncthreads();
-  if (work)
-    for (int a = 0; a < lane; ++a) M[a * q + lane] = M[lane * q + a];   // R = R^T
-  __syncthreads();
-  if (work)   // L^-T R: back substitution down column c
-    for (int a = q - 1; a >= 0; --a) {
-      double t = M[a * q + lane];
-      for (int k = a + 1; k < q; ++k) t = fma(-L[k * q + a], M[k * q + lane], t);
-      M[a * q + lane] = t / L[a * q + a];
-    }
-  __syncthreads();
-  if (work) {   // ... L^-1: back substitution along row r
-    double* const row = M + lane * q;
-    for (int a = q - 1; a >= 0; --a) {
-      double t = row[a];
-      for (int k = a + 1; k < q; ++k) t = fma(-L[k * q + a], row[k], t);
-      row[a] = t / L[a * q + a];
-    }
-  }
+  chol_adjoint(L, M, q, q, lane, work, [] { __syncthreads(); });
   __syncthreads();
   for (int e = tid; e < P * qq; e += QEHVI_THREADS) {
     const int j = e / qq, r = e - j * qq, i = r / q, k = r - i * q;
@@ -455,9 +412,9 @@ void launch_qehvi_tail(hipStream_t s, int P, int V, const double* bounds, const 
                        const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
                        double* out, int* info) {
   if (G <= 0) return;
-  if (P == 2) launch_qehvi_p<2>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, out, info);
-  else if (P == 3) launch_qehvi_p<3>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, out, info);
-  else launch_qehvi_p<4>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, out, info);
+  with_objectives(P, [&](auto PC) {
+    launch_qehvi_p<decltype(PC)::value>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, out, info);
+  });
 }
 
 // doubles beside the sample slots: the factors, the means, the adjoint work matrices, the sums of gmean and Lbar
@@ -478,12 +435,10 @@ void launch_qehvi_grad_tail(hipStream_t s, int P, int V, const double* bounds, c
                             const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
                             int zero_clipped, double* val, double* gmean, double* gcov, int* info) {
   if (G <= 0) return;
-  if (P == 2)
-    launch_qehvi_grad_p<2>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, zero_clipped, val, gmean, gcov, info);
-  else if (P == 3)
-    launch_qehvi_grad_p<3>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, zero_clipped, val, gmean, gcov, info);
-  else
-    launch_qehvi_grad_p<4>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, zero_clipped, val, gmean, gcov, info);
+  with_objectives(P, [&](auto PC) {
+    launch_qehvi_grad_p<decltype(PC)::value>(s, V, bounds, cells, K, mean, cov, G, gstride, q, eps, S, jitter, zero_clipped, val, gmean,
+                                             gcov, info);
+  });
 }
 
 }  // namespace tgp
