@@ -117,9 +117,10 @@ def _two_sum(a, b):
     return s, (a - (s - v)) + (b - v)
 
 
-def K_exact(kind, variance, ls, noise, X, X2=None, parts=False):
+def K_exact(kind, variance, ls, noise, X, X2=None, parts=False, grads=False):
     """K(X, X) + noise I (X2 None) or K(X, X2) in long double from the exact doubles, difference form.  ``parts``: also the
-    kernel-assembly bound E_K of the docstring (long double, same shape)."""
+    kernel-assembly bound E_K of the docstring (long double, same shape).  ``grads`` (tests/grad_resolution.py): instead
+    (K, dk/dr^2 (signed, without the noise), t [.., .., d] the scaled differences (x - x2) / ls, s the exponential's argument)."""
     assert kind in ("rbf", "matern52")
     ls = np.broadcast_to(np.asarray(ls, dtype=np.float64), (np.shape(X)[1],)).astype(LD)
     x = np.asarray(X, dtype=np.float64).astype(LD)
@@ -129,6 +130,7 @@ def K_exact(kind, variance, ls, noise, X, X2=None, parts=False):
     hi = np.zeros((a.shape[0], b.shape[0]), dtype=LD)           # r^2 = hi + lo
     lo = np.zeros_like(hi)
     w = np.zeros_like(hi)
+    T = np.zeros(hi.shape + (a.shape[1],), dtype=LD) if grads else None
     for c in range(a.shape[1]):
         diff = x[:, None, c] - x2[None, :, c]                   # exact: doubles of one binade range in a 64-bit significand
         q = diff / ls[c]
@@ -138,6 +140,8 @@ def K_exact(kind, variance, ls, noise, X, X2=None, parts=False):
         hi, e2 = _two_sum(hi, sq)
         lo += e2 + se + 2 * q * ql
         w += np.abs(q) * (np.abs(a[:, None, c]) + np.abs(b[None, :, c]))
+        if grads:
+            T[:, :, c] = q + ql
     r2 = hi + lo
     if kind == "rbf":
         s = r2 / 2
@@ -156,11 +160,16 @@ def K_exact(kind, variance, ls, noise, X, X2=None, parts=False):
         e = np.exp(-sh) * (1 - sl)
         K = var * ((1 + s + (vh + vl) / 3) * e)
         dr2 = var * LD(5) / 6 * (1 + s) * e
+    if grads:
+        assert not parts
+        dk = -dr2                                                   # (a new array: K's diagonal takes the noise below)
     E = EPS * ((A_AT(kind, a.shape[1]) + B_COEF(kind, a.shape[1]) * s) * K + dr2 * w)
     if X2 is None:
         i = np.arange(a.shape[0])
         K[i, i] += LD(noise)
         E[i, i] += EPS * (var + LD(noise))
+    if grads:
+        return K, dk, T, s
     return (K, E) if parts else K
 
 

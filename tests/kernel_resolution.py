@@ -28,7 +28,19 @@ sqrt(5) r).  Counted from the code path in units of eps (one rounding = eps / 2)
   -3/2 variance exp(-s): 3 + 1.5 = 4.5; matern52 -5/6 variance (1 + s) exp(-s): (1 + s) exp(-s) changes by
   s^2 / (1 + s) <= s times the relative error of s, which B s covers, leaving the addition's 1/2, the exponential's 2 and
   three products: 4 + 1.5 = 5.5.
-* the dense sum adds 17 eps for the summation (17 positive terms, condition 1), each term weighted with its own s."""
+* the dense sum adds 17 eps for the summation (17 positive terms, condition 1), each term weighted with its own s.
+* the variance chain in the exact one-point design (N = 1, K + noise = 4, W = 1/2 and variance 1: var = 1 - k^2 / 4 >= 3/4,
+  d var / dx = -k dk / 2), read through acq_value_grad("nlcb", 2): v = -(k - 2 sd), g_c = -dk_c + dvar_c / sd; with e_k = A + B s the
+  count of k and e_d = A_GRAD + B s that of dk (relative to |dk|_inf), `nlcb2_tolerances`:
+    C1 = k / 2 and Z = k / 4 are exact scalings; sum C1^2 is one fused product (1/2), the subtraction from 1 one rounding:
+        d var = eps [k^2 / 2 e_k + k^2 / 8 + var / 2]
+    sd = sqrt(var) at its claimed 2 ulp:  d sd = d var / (2 sd) + 2 eps sd;  2 sd is exact, the subtraction and the sign 1/2:
+        d v = eps e_k k + 2 d sd + eps / 2 |v|
+    dv/dvar = 2 / (2 sd): the division 1/2 and sd's own relative error;  dvar_c = -2 (k / 4) dk_c: Z's e_k, dk's e_d, one fused
+    product (1/2);  g_c = -dk_c + dvar_c / sd: two products and an addition, at most 1 eps of each term:
+        d g_c = eps e_d |dk|_inf (1 + k / (2 sd)) + |dvar_c| / sd (eps (e_k + 1) + d sd / sd) + eps (|dk_c| + |dvar_c| / sd)."""
+import numpy as np
+
 
 KINDS = ("rbf", "matern12", "matern32", "matern52")
 D_EFF = 3   # coordinates in which probe and training point differ (also in the d = 40 copy)
@@ -41,3 +53,26 @@ B_TRAJ = dict(rbf=(D_EFF + 4) / 2, matern12=(D_EFF + 4) / 4 + TRAJ_SQRT, matern3
 # caps: A <= 8 and, for every path but the trajectory's Matern short form, B <= (d + 19) / 4
 assert max(max(A_COEF.values()), max(A_GRAD.values())) <= 8.0
 assert max(max(B_DIFF.values()), B_TRAJ["rbf"]) <= (D_EFF + 19) / 4
+
+
+def nlcb2_tolerances(kind, B, k, s, dk):
+    """(v, g, tol_v, tol_g) of acq_value_grad("nlcb", 2) in the exact one-point design from the goldens' k [M], s [M], dk [M, 3]:
+    the closed form in long double and the tolerances counted in the module docstring (float64)."""
+    LD = np.longdouble
+    eps = 2.0 ** -52
+    kl, dkl = np.asarray(k, dtype=LD), np.asarray(dk, dtype=LD)
+    var = 1 - kl * kl / 4
+    sd = np.sqrt(var)
+    v = -(kl - 2 * sd)
+    dvar = -(kl / 2)[:, None] * dkl
+    g = -dkl + dvar / sd[:, None]
+    k, s, dk, varf, sdf = (np.asarray(a, dtype=np.float64) for a in (k, s, dk, var, sd))
+    e_k, e_d = A_COEF[kind] + B * s, A_GRAD[kind] + B * s
+    d_var = eps * (k * k / 2 * e_k + k * k / 8 + varf / 2)
+    d_sd = d_var / (2 * sdf) + 2 * eps * sdf
+    tol_v = eps * e_k * k + 2 * d_sd + eps / 2 * np.abs(np.asarray(v, dtype=np.float64))
+    advar = np.abs(np.asarray(dvar, dtype=np.float64)) / sdf[:, None]
+    dk_inf = np.abs(dk).max(axis=1)
+    tol_g = ((eps * e_d * dk_inf * (1 + k / (2 * sdf)))[:, None] + advar * (eps * (e_k + 1) + d_sd / sdf)[:, None]
+             + eps * (np.abs(dk) + advar))
+    return v, g, tol_v, tol_g

@@ -22,7 +22,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.kernel_resolution import A_COEF, A_GRAD, B_DIFF, B_TRAJ, KINDS
+from tests.kernel_resolution import A_COEF, A_GRAD, B_DIFF, B_TRAJ, KINDS, nlcb2_tolerances
 from tests.util import EPS, record_margin
 
 pytestmark = pytest.mark.gpu
@@ -90,6 +90,26 @@ class Checker:
             i = int(np.argmax((err / np.where(tol > 0, tol, 1e-320)).max(axis=1)))
             self.bad.append(f"{what}: worst/tol {worst:.3g} at s={p.s[n][i]:.4g}: got {got[n][i]} ref {ref[i]}")
 
+    def nlcb2(self, what, val, grad, p):
+        """The variance chain: value and gradient of -LCB at beta = 2 against the closed form of the exact one-point design
+        (tests/kernel_resolution.py nlcb2_tolerances); at the underflow probes k = dk = 0: v = 2 sd = 2, g = 0."""
+        val, grad = np.asarray(val, dtype=np.float64).reshape(-1), np.asarray(grad, dtype=np.float64).reshape(len(p.k), -1)
+        if not (np.all(np.isfinite(val)) and np.all(np.isfinite(grad))):
+            self.bad.append(f"{what}: non-finite values")
+            return
+        if not np.all(grad[:, 3:] == 0.0):
+            self.bad.append(f"{what}: gradient along coordinates that do not differ")
+        if not np.all(np.abs(grad[p.under]) <= 1e-290):
+            self.bad.append(f"{what}: gradient at the underflow probes {grad[p.under][:2]}")
+        v, g, tol_v, tol_g = nlcb2_tolerances(self.base, self.B, p.k, p.s, p.dk)
+        for name, got, ref, tol, rows in (("value", val, v, tol_v, np.ones_like(p.under)), ("gradient", grad[:, :3], g, tol_g, ~p.under)):
+            got, ref, tol, s = got[rows], ref[rows], tol[rows], p.s[rows]
+            err = np.abs(np.asarray(got - ref, dtype=np.float64))
+            worst = record_margin(f"{self.kind} {what} {name}", err, tol)
+            if not np.all(err <= tol):
+                i = int(np.argmax((err / np.where(tol > 0, tol, 1e-320)).reshape(len(s), -1).max(axis=1)))
+                self.bad.append(f"{what} {name}: worst/tol {worst:.3g} at s={s[i]:.4g}: got {got[i]} ref {np.asarray(ref[i], dtype=np.float64)}")
+
     def done(self):
         assert not self.bad, f"{self.kind}: {len(self.bad)} path(s) outside eps (A + B s):\n" + "\n".join(self.bad)
 
@@ -132,6 +152,7 @@ def _difference_form_paths(chk, make, p, d, joint=True):
         chk.gradients(f"d={d} acq_value_grad gradient", np.asarray(grad)[:, :3], p, sign=-1.0)
         if d > 3:
             assert np.all(np.asarray(grad)[:, 3:] == 0.0), "gradient along coordinates that do not differ"
+        chk.nlcb2(f"d={d} acq_value_grad nlcb(2)", *eng.acq_value_grad("nlcb", 2.0, x), p)
     chk.values(f"d={d} M={M} predict (sweep)", make(1024).predict(x)[0], p)
     for v, name in VARIANTS:
         chk.values(f"d={d} M={M} nlcb values ({name})", -np.asarray(make(v).acq_values("nlcb", 0.0, x)), p)
