@@ -430,6 +430,22 @@ int tgp_qehvi_value_grad(const tgp_handle* hs, int P, const double* Xq, int64_t 
 int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S,
                         double jitter, double* out, int where);
 
+/* The Monte-Carlo qEI tails alone, on caller-supplied moments AS THE MODEL RETURNS THEM (the entry adds the jitter); they need no
+ * data on the handle.  mean [G,q], cov [G,q,q] (the lower triangle and the diagonal are read), eps [q,S], all host or all
+ * device by `where`; 1 <= q <= 64 else TGP_ERR_SHAPE, S >= 1 and jitter >= 0 else TGP_ERR_ARG, any G >= 0 (G = 0 does nothing).
+ *   tgp_qei_moments: out [G] = tgp_qei's value of those moments, from the same kernel; samples NULL or [G,S,q] = what
+ *     tgp_reparam_samples returns for them (one launch writes both).  Chunks of 2^30 / (8 q^2) groups, with samples of
+ *     2^28 / (8 q max(q, S)).
+ *   tgp_qei_moments_grad: val [G] = tgp_qei_moments' value bit for bit, gmean [G,q] = d val / d mean = -(the number of improving
+ *     draws whose smallest sample is point i, the FIRST such point on a tie) / S, gcov [G,q,q] SYMMETRIC with
+ *     d val = sum_ij gcov_ij dcov_ij for every symmetric dcov; gcov_ii = 0 where cov_ii <= 1e-12 (the posterior's clip).  A draw
+ *     whose improvement eta - min is exactly 0 counts as not improving.  The LDS bound of tgp_qei_value_grad, else TGP_ERR_SHAPE.
+ * TGP_ERR_NOT_PD names a group as tgp_qei does; the kernel has then gone on with pivot 1 and every output is written. */
+int tgp_qei_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S, double eta,
+                    double jitter, double* out, double* samples, int where);
+int tgp_qei_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
+                         double eta, double jitter, double* val, double* gmean, double* gcov, int where);
+
 /* == value and gradient of a BATCH acquisition function at the handful of q-batches an L-BFGS-B iteration holds: the reference
  * optimises BatchMonteCarloExpectedImprovement through batchify_joint(generate_continuous_optimizer) (acquisition/optimizer.py:
  * 897-934, 344-560) with tfp.math.value_and_gradient (optimizer.py:628-629), i.e. autodiff THROUGH predict_joint

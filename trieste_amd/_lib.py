@@ -75,6 +75,9 @@ SIGNATURES = {
     "tgp_qehvi_moments_grad": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, C.c_int]),
     "tgp_qehvi_value_grad": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, C.c_int]),
     "tgp_reparam_samples": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_int]),
+    "tgp_qei_moments": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, C.c_int]),
+    "tgp_qei_moments_grad": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp,
+                                       C.c_int]),
     "tgp_traj_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_create_rff": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_get_theta": (C.c_int, [_vp, _vp]),

@@ -2683,6 +2683,76 @@ int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const 
                            });
 }
 
+// ---- the Monte-Carlo qEI tails on given moments: tgp_batch_ei_moments' / tgp_batch_ei_moments_grad's body around them ------------
+static int qei_moments_check(tgp_handle h, int64_t G, int q, const double* eps, int S, double jitter) {
+  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
+  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  if (q < 1 || q > MAX_Q) return fail(h, TGP_ERR_SHAPE, "q must be in 1..%d, got %d", MAX_Q, q);
+  if (G < 0) return fail(h, TGP_ERR_ARG, "bad arguments");
+  return TGP_OK;
+}
+
+int tgp_qei_moments(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S, double eta,
+                    double jitter, double* out, double* samples, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = qei_moments_check(h, G, q, eps, S, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!mean || !cov || !out) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  const double* deps;
+  if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
+  // tgp_qei's chunk rule, with the samples tgp_reparam_samples'
+  const int64_t chunk = samples ? std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)q * std::max(q, S) * 8))
+                                : std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
+  return for_group_chunks(h, G, chunk, true, QEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    // host residency: the moments through s_out1 / s_out2, the value through s_out3, the samples through s_ent (idle here)
+    const size_t ns = (size_t)gc * S * q;
+    double* const sam = samples ? samples + g0 * S * q : nullptr;
+    const double *dmean, *dcov;
+    double *dout, *dsam;
+    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, (size_t)gc * q, where, &dmean)) return rc;
+    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, (size_t)gc * q * q, where, &dcov)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_out3, out + g0, (size_t)gc, where, &dout)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_ent, sam, ns, where, &dsam)) return rc;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // the events bracket the tail itself
+    launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, eta, jitter, dout, dsam, h->d_info.as<int>());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    if (int rc = stage_out_finish(h, dsam, sam, ns, where)) return rc;
+    return stage_out_finish(h, dout, out + g0, (size_t)gc, where);
+  });
+}
+
+int tgp_qei_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
+                         double eta, double jitter, double* val, double* gmean, double* gcov, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = qei_moments_check(h, G, q, eps, S, jitter)) return rc;
+  if (qei_grad_tail_lds_bytes(q, S) > (size_t)160 * 1024)   // (tgp_qei_value_grad's refusal)
+    return fail(h, TGP_ERR_SHAPE, "q = %d with S = %d draws does not fit the tail's LDS", q, S);
+  if (G == 0) return TGP_OK;
+  if (!mean || !cov || !val || !gmean || !gcov) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  const double* deps;
+  if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
+  return for_group_chunks(h, G, chunk, true, QEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    // host residency as in tgp_batch_ei_moments_grad: the two adjoints through s_in and s_ent
+    const size_t nm = (size_t)gc * q, nc = (size_t)gc * q * q;
+    const double *dmean, *dcov;
+    double *dval, *dgm, *dgc;
+    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, nm, where, &dmean)) return rc;
+    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, nc, where, &dcov)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_out3, val + g0, (size_t)gc, where, &dval)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_in, gmean + g0 * q, nm, where, &dgm)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_ent, gcov + g0 * q * q, nc, where, &dgc)) return rc;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // the events bracket the tail itself
+    launch_qei_grad_tail(h->stream, dmean, dcov, gc, q, deps, S, eta, jitter, dval, dgm, dgc, h->d_info.as<int>());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    if (int rc = stage_out_finish(h, dval, val + g0, (size_t)gc, where)) return rc;
+    if (int rc = stage_out_finish(h, dgm, gmean + g0 * q, nm, where)) return rc;
+    return stage_out_finish(h, dgc, gcov + g0 * q * q, nc, where);
+  });
+}
+
 // ---- trajectories -----------------------------------------------------------------------------
 static TrajDev traj_dev(tgp_traj t) {
   TrajDev td;

@@ -814,6 +814,44 @@ def batch_ei_moments_grad(engine, mean, cov, w1, w2, eta: float):
     return val, gm, gc
 
 
+def _qei_moment_args(mean, cov, eps):
+    m, c, e = _Arg(mean), _Arg(cov), _Arg(eps)
+    if len(m.shape) != 2 or c.shape != m.shape + (m.shape[-1],):
+        raise ValueError(f"mean must be [G, q] and cov [G, q, q], got {m.shape} and {c.shape}")
+    G, q = m.shape
+    if not 1 <= q <= 64:
+        raise ValueError(f"the Monte-Carlo qEI takes 1 <= q <= 64 points per batch, got {q}")
+    if len(e.shape) != 2 or e.shape[0] != q or e.shape[1] < 1:
+        raise ValueError(f"eps must be [q={q}, S >= 1], got {e.shape}")
+    if m.where != c.where or m.where != e.where:
+        raise ValueError("mean, cov and eps must live in the same place (all host or all device)")
+    return m, c, e, G, q, e.shape[1]
+
+
+def qei_moments(engine, mean, cov, eps, eta: float, jitter: float = 1e-6, samples: bool = False):
+    """The Monte-Carlo qEI tail on caller-supplied moments: mean [G, q], cov [G, q, q] as a model's ``predict_joint`` returns
+    them, eps [q, S] -> value [G] (``GPEngine.qei``'s, from the same kernel); with ``samples=True`` -> (value, samples
+    [G, S, q]), the samples being ``GPEngine.reparam_samples``' (tgp_qei_moments).  Needs no data on the engine."""
+    m, c, e, G, q, S = _qei_moment_args(mean, cov, eps)
+    out, po = GPEngine._out(m, (G,))
+    sam, ps = GPEngine._out(m, (G, S, q)) if samples else (None, None)
+    engine._chk(engine._lib.tgp_qei_moments(engine._h, m.ptr, c.ptr, G, q, e.ptr, S, float(eta), float(jitter), po, ps, m.where))
+    return (out, sam) if samples else out
+
+
+def qei_moments_grad(engine, mean, cov, eps, eta: float, jitter: float = 1e-6):
+    """The tail with its adjoints on caller-supplied moments -> (value [G], gmean [G, q], gcov [G, q, q]) with gcov symmetric,
+    d value = sum gcov * dcov for every symmetric dcov (tgp_qei_moments_grad); (q, S) within ``GPEngine.qei_value_grad_fits``.
+    Needs no data on the engine."""
+    m, c, e, G, q, S = _qei_moment_args(mean, cov, eps)
+    val, pv = GPEngine._out(m, (G,))
+    gm, pgm = GPEngine._out(m, (G, q))
+    gc, pgc = GPEngine._out(m, (G, q, q))
+    engine._chk(engine._lib.tgp_qei_moments_grad(engine._h, m.ptr, c.ptr, G, q, e.ptr, S, float(eta), float(jitter), pv, pgm, pgc,
+                                                 m.where))
+    return val, gm, gc
+
+
 def batch_ei_value_grad(engine, Xq, w1, w2, eta: float):
     """Xq [G, q, d] (2 <= q <= 16, G * q <= 2048) -> (analytic batch EI [G], its gradient [G, q, d]) in one device call:
     the joint posterior, the tail with its moment adjoints and the posterior's vector-Jacobian product
