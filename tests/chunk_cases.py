@@ -20,7 +20,12 @@ comparison of the GPU test applies the probes' largest tolerance to EVERY group.
 the probe sets, 1.8e-3 over the same 3000 random groups.
 
 The two entries on given moments: the mean is distinct per group, the covariance is bank[g % 257], a bank of 257 matrices
-drawn as tests/test_gpu_batch_ei.py draws its random moments (257 is prime: the pattern does not repeat with the chunk)."""
+drawn as tests/test_gpu_batch_ei.py draws its random moments (257 is prime: the pattern does not repeat with the chunk).
+
+The four newer chunked entries on given moments (tgp_qei_moments, tgp_qei_moments_grad, tgp_qehvi_moments,
+tgp_qehvi_moments_grad) have rows of their own, MOMENTS_ROWS, for tests/test_gpu_moments_chunks.py: G = chunk + 3 groups, mean
+AND covariance of group g are those of group g % 257 of a bank of 257 distinct groups, and the expected output is the output of
+one small call on the bank, tiled the same way (``moments_row_inputs``, ``tiled``)."""
 from __future__ import annotations
 
 import functools
@@ -53,6 +58,44 @@ def chunk_moments_grad(q: int, S: int = 0) -> int:        # tgp_batch_ei_moments
 
 def chunk_reparam(q: int, S: int) -> int:                 # tgp_reparam_samples
     return max(1, 2 ** 28 // (q * max(q, S) * 8))
+
+
+def chunk_qei_moments(q: int, S: int = 0, samples: bool = False) -> int:   # tgp_qei_moments; tgp_qei_moments_grad (no samples)
+    return chunk_reparam(q, S) if samples else chunk_qei(q)
+
+
+def chunk_qehvi(P: int, q: int) -> int:                   # tgp_qehvi_moments (qehvi_group_chunk), tgp_qehvi_values
+    return max(1, 2 ** 28 // (8 * P * q * (q + 1)))
+
+
+def chunk_qehvi_grad(P: int, q: int) -> int:              # tgp_qehvi_moments_grad
+    return max(1, chunk_qehvi(P, q) // 2)
+
+
+@dataclass(frozen=True)
+class MomentsRow:
+    """A row of tests/test_gpu_moments_chunks.py: a chunked entry on given moments at G = chunk + 3 groups."""
+    entry: str
+    q: int
+    S: int
+    P: int          # objectives of the stacked arrays (1: the qEI entries)
+    samples: bool
+    chunk: int      # the restated rule at this shape
+
+    @property
+    def G(self) -> int:
+        return self.chunk + 3
+
+
+MOMENTS_ROWS = {r_id: MomentsRow(*r) for r_id, r in {
+    "qei_moments": ("qei_moments", 64, 4, 1, False, chunk_qei_moments(64, 4)),
+    "qei_moments-samples": ("qei_moments", 64, 3, 1, True, chunk_qei_moments(64, 3, samples=True)),
+    "qei_moments_grad": ("qei_moments_grad", 64, 4, 1, False, chunk_qei_moments(64, 4)),
+    "qehvi_moments": ("qehvi_moments", 8, 1, 2, False, chunk_qehvi(2, 8)),
+    "qehvi_moments_grad": ("qehvi_moments_grad", 8, 1, 2, False, chunk_qehvi_grad(2, 8)),
+}.items()}
+TABLE_MOMENTS_CHUNKS = {"qei_moments": 32768, "qei_moments-samples": 8192, "qei_moments_grad": 32768, "qehvi_moments": 233016,
+                        "qehvi_moments_grad": 116508}
 
 
 @dataclass(frozen=True)
@@ -193,6 +236,31 @@ MOMENTS_G = max(g_max(e) for e in ENTRIES.values() if not e.posterior)
 def moments_eta(q: int) -> float:
     """The median of the row minima, as in tests/test_gpu_batch_ei.py."""
     return float(np.median(moment_means(q, MOMENTS_G).min(axis=1)))
+
+
+# ---- the rows of the four newer entries on given moments ----------------------------------------------------------------------
+TWO_CELLS = (np.array([[-10.0, -10.0], [0.5, -10.0]]), np.array([[0.5, 1.5], [1.5, 0.5]]))   # left of the front {(0.5, 0.5)}
+
+
+@functools.lru_cache(maxsize=None)
+def moments_row_inputs(row_id: str):
+    """(mean bank [257, q] or [P, 257, q], cov bank [257, q, q] or [P, 257, q, q], eps [q, S] or [P, q, S], eta) of a row: 257
+    distinct well-conditioned groups.  Read-only."""
+    r = MOMENTS_ROWS[row_id]
+    rng = np.random.default_rng([4444, r.q, r.S, r.P])
+    lead = (BANK,) if r.P == 1 else (r.P, BANK)
+    A = rng.standard_normal(lead + (r.q, r.q))
+    cov = A @ np.swapaxes(A, -1, -2) / r.q + 0.1 * np.eye(r.q)
+    mean = rng.standard_normal(lead + (r.q,)) if r.P == 1 else rng.uniform(0.0, 1.0, lead + (r.q,))
+    eps = rng.standard_normal((r.q, r.S) if r.P == 1 else (r.P, r.q, r.S))
+    for a in (mean, cov, eps):
+        a.setflags(write=False)
+    return mean, cov, eps, float(np.median(mean.min(axis=-1)))
+
+
+def tiled(bank: np.ndarray, G: int, stacked: bool) -> np.ndarray:
+    """bank [257, ...] -> [G, ...] with out[g] = bank[g % 257]; stacked: bank [P, 257, ...] -> out[j, g] = bank[j, g % 257]."""
+    return np.take(bank, np.arange(G) % BANK, axis=1 if stacked else 0)
 
 
 # ---- references -----------------------------------------------------------------------------------------------------------

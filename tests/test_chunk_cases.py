@@ -19,6 +19,34 @@ def test_restated_rules_give_the_chunk_sizes_of_the_table():
     assert CC.chunk_qei(20000) == CC.chunk_moments_grad(20000) == CC.chunk_reparam(20000, 1) == 1
 
 
+def test_restated_rules_give_the_chunk_sizes_of_the_moments_rows():
+    """The four newer chunked entries on given moments (tests/test_gpu_moments_chunks.py)."""
+    assert {n: r.chunk for n, r in CC.MOMENTS_ROWS.items()} == CC.TABLE_MOMENTS_CHUNKS
+    assert all(r.G == r.chunk + 3 and -(-r.G // r.chunk) == 2 for r in CC.MOMENTS_ROWS.values())
+    # the rules themselves, away from the table's shapes
+    assert CC.chunk_qei_moments(5, 100) == CC.chunk_qei(5) and CC.chunk_qei_moments(5, 100, samples=True) == CC.chunk_reparam(5, 100)
+    assert CC.chunk_qehvi(2, 8) == 2 ** 28 // (8 * 2 * 8 * 9) and CC.chunk_qehvi(4, 1) == 2 ** 28 // 64
+    assert CC.chunk_qehvi_grad(4, 1) == 2 ** 21 and CC.chunk_qehvi(4, 6000) == CC.chunk_qehvi_grad(4, 6000) == 1
+    # the gradient row's shape fits the qEI gradient tail's LDS (GPEngine.qei_value_grad_fits restates the bound)
+    r = CC.MOMENTS_ROWS["qei_moments_grad"]
+    assert 8 * (2 * r.q * (r.q | 1) + 128) + 4 * ((r.S + 1) & ~1) == 67600 <= 160 * 1024
+
+
+def test_the_moments_rows_tile_a_bank_of_distinct_groups():
+    for rid, r in CC.MOMENTS_ROWS.items():
+        mean, cov, eps, _ = CC.moments_row_inputs(rid)
+        stacked = r.P > 1
+        lead = (r.P, CC.BANK) if stacked else (CC.BANK,)
+        assert mean.shape == lead + (r.q,) and cov.shape == lead + (r.q, r.q)
+        assert eps.shape == ((r.P, r.q, r.S) if stacked else (r.q, r.S))
+        flat = np.moveaxis(mean, -2, 0).reshape(CC.BANK, -1)
+        assert len(np.unique(flat, axis=0)) == CC.BANK
+        assert np.linalg.eigvalsh(cov).min() >= 0.1 - 1e-12
+        t = CC.tiled(mean, 2 * CC.BANK + 5, stacked)
+        g = np.array([0, 1, CC.BANK - 1, CC.BANK, 2 * CC.BANK + 4])
+        np.testing.assert_array_equal(np.take(t, g, axis=1 if stacked else 0), np.take(mean, g % CC.BANK, axis=1 if stacked else 0))
+
+
 def test_every_case_crosses_the_boundary_as_intended():
     assert len(CC.CASES) == 12
     for c in CC.CASES:

@@ -1,7 +1,8 @@
 """Development aid: checksums of what the host layer's small-call paths return (tgp_api.hip: the small-product posterior, the
 group-chunk loop, the calls on given moments) where tests/history_tour.py and tests/ehvi_tour.py do not reach -- host- AND
 device-resident arguments, a wide model, a repulsion twin whose padded size differs from the model's, G q = 2048 exactly, a
-tgp_qei of two chunks, and every tgp_ehvi_* / tgp_qehvi_* entry on small stacks (both residencies, private streams, a handle
+tgp_qei of two chunks, tgp_qei_moments / tgp_qei_moments_grad beside the batch EI calls on given moments, a host-resident
+tgp_qei_moments and tgp_qehvi_moments of two chunks each, and every tgp_ehvi_* / tgp_qehvi_* entry on small stacks (both residencies, private streams, a handle
 named twice, a group that is not positive definite).  Run under two builds (TGP_LIB=...) and diff the output: a change that only moves host code or
 scratch addresses must leave every line identical."""
 import sys, os, hashlib
@@ -75,6 +76,36 @@ for where, put in (("host", lambda *xs: xs), ("dev", dev)):
     print("moments", where, "batch_ei_moments", h(E.batch_ei_moments(eng, m, c, a1, a2, 0.3)))
     print("moments", where, "batch_ei_moments_grad", h(*E.batch_ei_moments_grad(eng, m, c, a1, a2, 0.3)))
     print("moments", where, "ehvi_moments", h(E.ehvi_moments(eng, pm, pv)), flush=True)
+epq = rng.standard_normal((q, S))
+for where, put in (("host", lambda *xs: xs), ("dev", dev)):
+    m, c, e = put(mean, cov, epq)
+    print("moments", where, "qei_moments", h(E.qei_moments(eng, m, c, e, 0.3)))
+    print("moments", where, "qei_moments samples", h(*E.qei_moments(eng, m, c, e, 0.3, samples=True)))
+    print("moments", where, "qei_moments_grad", h(*E.qei_moments_grad(eng, m, c, e, 0.3)), flush=True)
+
+def said_of(call):
+    """code (the exception's type) and message of a call that fails"""
+    try:
+        call()
+        said = "no error"
+    except Exception as err:
+        said = f"{type(err).__name__}: {err}"
+    return hashlib.sha256(said.encode()).hexdigest()[:16] + " " + said
+
+bad = cov.copy(); bad[7] = -bad[7]
+print("moments not PD qei_moments", said_of(lambda: E.qei_moments(eng, mean, bad, epq, 0.3)))
+print("moments not PD qei_moments_grad", said_of(lambda: E.qei_moments_grad(eng, mean, bad, epq, 0.3)), flush=True)
+
+# two chunks on given moments, host-resident (the gather path): group g's moments are those of group g % 257 of a bank
+def two_chunks(name, fn, lead, G, q, eps, *rest):
+    A = rng.standard_normal(lead + (257, q, q))
+    bank_m, bank_c = rng.uniform(0.0, 1.0, lead + (257, q)), A @ np.swapaxes(A, -1, -2) / q + 0.1 * np.eye(q)
+    idx = np.arange(G) % 257
+    out = fn(eng, np.take(bank_m, idx, axis=len(lead)), np.take(bank_c, idx, axis=len(lead)), eps, *rest)
+    print("moments two chunks", name, h(out), eng.last_kernel_ms()[1], flush=True)
+
+two_chunks("qei_moments", E.qei_moments, (), 32768 + 3, 64, rng.standard_normal((64, 4)), 0.3)    # 2^30 / (64 * 64 * 8) groups
+two_chunks("qehvi_moments", E.qehvi_moments, (2,), 233016 + 3, 8, rng.standard_normal((2, 8, 1)))   # 2^28 / (8 * 2 * 8 * 9)
 eng.close()
 
 # the multi-objective entries (tgp_ehvi_*, tgp_qehvi_*) on small stacks: P = 2 and P = 4 members, N = 130, d = 3, a table
@@ -147,12 +178,7 @@ for P in (2, 4):
     cov[P - 1, 5] = -cov[P - 1, 5]
     e = rng.standard_normal((P, 4, 40))
     for name, fn in (("qehvi_moments", E.qehvi_moments), ("qehvi_moments_grad", E.qehvi_moments_grad)):
-        try:
-            fn(engines[0], mean, cov, e)
-            said = "no error"
-        except Exception as err:
-            said = f"{type(err).__name__}: {err}"
-        print(f"stack P={P} not PD", name, hashlib.sha256(said.encode()).hexdigest()[:16], said, flush=True)
+        print(f"stack P={P} not PD", name, said_of(lambda: fn(engines[0], mean, cov, e)), flush=True)
     for e in engines:
         e.close()
 

@@ -15,6 +15,7 @@
 #include <new>
 #include <string>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <vector>
@@ -128,6 +129,16 @@ int info_finish(tgp_handle h, const char* fmt, int64_t g0 = 0) {
   if (info != 0) return fail(h, TGP_ERR_NOT_PD, fmt, (long long)(g0 + info - 1));
   return TGP_OK;
 }
+
+// the two refusals every entry that draws samples shares (each entry keeps its own place for them among its checks)
+int check_draws(tgp_handle h, double jitter, const double* eps, int S) {
+  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
+  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  return TGP_OK;
+}
+
+// does the qEI gradient tail's LDS (one wave per group, S sample slots) hold this shape?
+bool qei_grad_tail_fits(int q, int S) { return qei_grad_tail_lds_bytes(q, S) <= (size_t)160 * 1024; }
 
 // One scratch buffer as a list of arrays: the caller names each pointer and its element count, the ONE reserve and the
 // pointers both come from that list (tgp_host.hpp scratch_offsets).  An array of count 0 gets a pointer nobody may use.
@@ -2206,11 +2217,10 @@ int tgp_joint_vjp(tgp_handle h, const double* Xq, int64_t G, int q, const double
 int tgp_qei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S, double eta, double jitter,
                        double* val, double* grad, int where) {
   if (!h) return TGP_ERR_ARG;
-  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
-  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  if (int rc = check_draws(h, jitter, eps, S)) return rc;
   if (!val || !grad) return fail(h, TGP_ERR_ARG, "val / grad is NULL");
   if (q > MAX_Q) return fail(h, TGP_ERR_SHAPE, "q must be in 1..%d, got %d", MAX_Q, q);
-  if (q >= 1 && qei_grad_tail_lds_bytes(q, S) > (size_t)160 * 1024)
+  if (q >= 1 && !qei_grad_tail_fits(q, S))
     return fail(h, TGP_ERR_SHAPE, "q = %d with S = %d draws does not fit the tail's LDS (tgp_joint_forward / tgp_joint_vjp take any S)", q, S);
   const double* dXq;
   int64_t P, Ppad;
@@ -2531,6 +2541,85 @@ int joint_tail_chunks(tgp_handle h, const double* Xq, int64_t G, int q, int64_t 
   });
 }
 
+// groups per chunk: a group's `doubles_per_group` doubles of scratch stay within `budget_bytes`
+int64_t groups_within(uint64_t budget_bytes, int64_t doubles_per_group) {
+  return std::max<int64_t>(1, (int64_t)(budget_bytes / (uint64_t)(8 * doubles_per_group)));
+}
+// the [G,q,q] covariances within 1 GiB (tgp_qei, tgp_batch_ei and the value tails on given moments)
+int64_t joint_group_chunk(int q) { return groups_within(1ull << 30, (int64_t)q * q); }
+// ... with the [G,S,q] samples next to them, each within 256 MiB (tgp_reparam_samples, tgp_qei_moments with samples)
+int64_t samples_group_chunk(int q, int S) { return groups_within(1ull << 28, (int64_t)q * std::max(q, S)); }
+// the stacked moments of a chunk, 8 P (q + q^2) bytes per group, within 256 MiB (the qEHVI entries)
+int64_t qehvi_group_chunk(int P, int q) { return groups_within(1ull << 28, (int64_t)P * q * (q + 1)); }
+
+// a launch on the handle's stream between its two events (ehvi_read_tail_ms and for_group_chunks read them): enqueue only
+template <class Launch>
+int bracketed(tgp_handle h, Launch launch) {
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch();
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return TGP_OK;
+}
+
+// The arrays of a call on given moments.  Each is obj x G x n doubles of the caller's (obj: 1, or the partition's P for the
+// stacked multi-objective arrays), an input or an output (null: an optional output nobody asked for).  Under host residency
+// they pass through these buffers: mean -> s_out1, cov / var -> s_out2, the value -> s_out3, and the two adjoints (or the
+// samples) -> s_in and s_ent, which are idle in a call on given moments: no candidates, no entropy tail.
+struct MomentArray {
+  double* host;
+  bool input;
+  DevBuf* buf;
+  int obj;
+  int64_t n;
+  double* dev;   // where the tail finds the chunk's groups (stage_chunk)
+};
+enum { M_MEAN, M_COV, M_VAL, M_GMEAN, M_GCOV, M_ARRAYS, M_SAMPLES = M_GCOV };   // (the samples take the idle adjoint's place)
+using MomentArrays = std::array<MomentArray, M_ARRAYS>;
+// mean [obj][G][nm], cov [obj][G][nc] -> val [G], and with adjoints gmean, gcov in the inputs' shapes
+MomentArrays moment_arrays(tgp_handle h, int obj, int64_t nm, int64_t nc, const double* mean, const double* cov, double* val,
+                           double* gmean = nullptr, double* gcov = nullptr) {
+  return {{{const_cast<double*>(mean), true, &h->s_out1, obj, nm, nullptr}, {const_cast<double*>(cov), true, &h->s_out2, obj, nc, nullptr},
+           {val, false, &h->s_out3, 1, 1, nullptr}, {gmean, false, &h->s_in, obj, nm, nullptr}, {gcov, false, &h->s_ent, obj, nc, nullptr}}};
+}
+
+// The groups g0 .. g0 + gc of a call of G groups around the tail.  Device residency: the caller's arrays at g0, nothing copied
+// (group stride G).  Host residency: in front of the tail (`before`) each array's buffer reserved for the chunk as [obj][gc][n]
+// (group stride gc) and the inputs copied in, behind it the outputs copied back -- a copy per objective, one in all where the
+// chunk is the whole call and the array contiguous.  Enqueue only.
+int stage_chunk(tgp_handle h, MomentArrays& m, int64_t g0, int64_t gc, int64_t G, int where, bool before) {
+  for (MomentArray& a : m) {
+    if (!a.host) continue;
+    if (where == TGP_DEVICE) {
+      a.dev = a.host + g0 * a.n;
+      continue;
+    }
+    if (before) {
+      HIPCHK(h, a.buf->reserve((size_t)a.obj * gc * a.n * sizeof(double)));
+      a.dev = a.buf->as<double>();
+    }
+    if (a.input != before) continue;
+    const int pieces = gc == G ? 1 : a.obj;
+    const size_t len = (size_t)(a.obj / pieces) * gc * a.n;
+    for (int j = 0; j < pieces; ++j) {
+      double *const d = a.dev + (size_t)j * len, *const s = a.host + ((int64_t)j * G + g0) * a.n;
+      HIPCHK(h, before ? hipMemcpyAsync(d, s, len * sizeof(double), hipMemcpyHostToDevice, h->stream)
+                       : hipMemcpyAsync(s, d, len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  return TGP_OK;
+}
+
+// for_group_chunks over a call on given moments: per chunk the arrays staged, `tail(gc, gstride)` -- a bracketed launch on the
+// arrays' `dev` -- and the outputs brought back
+template <class Tail>
+int moments_chunks(tgp_handle h, int64_t G, int64_t chunk, const char* not_pd, int where, MomentArrays& m, Tail tail) {
+  return for_group_chunks(h, G, chunk, true, not_pd, [&](int64_t g0, int64_t gc) -> int {
+    if (int rc = stage_chunk(h, m, g0, gc, G, where, true)) return rc;
+    if (int rc = tail(gc, where == TGP_DEVICE ? G : gc)) return rc;
+    return stage_chunk(h, m, g0, gc, G, where, false);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -2538,16 +2627,13 @@ extern "C" {
 int tgp_qei(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S, double eta,
             double jitter, double* out, int where) {
   if (!h) return TGP_ERR_ARG;
-  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
-  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  if (int rc = check_draws(h, jitter, eps, S)) return rc;
   if (G == 0) return TGP_OK;
   if (!out) return fail(h, TGP_ERR_ARG, "out is NULL");
-  // chunk the groups so the [G,q,q] covariances stay within a bounded scratch (<= ~1 GiB)
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
   if (int rc = set_device(h)) return rc;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
-  return joint_tail_chunks(h, Xq, G, q, chunk, out, 1, where, true, QEI_NOT_PD,
+  return joint_tail_chunks(h, Xq, G, q, joint_group_chunk(q), out, 1, where, true, QEI_NOT_PD,
                            [&](const double* dmean, const double* dcov, int64_t gc, double* dout) {
                              launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, eta, jitter, dout, nullptr, h->d_info.as<int>());
                            });
@@ -2583,12 +2669,11 @@ int tgp_batch_ei(tgp_handle h, const double* Xq, int64_t G, int q, const double*
   if (int rc = bei_check(h, q, w1, w2, S)) return rc;
   if (G == 0) return TGP_OK;
   if (!out) return fail(h, TGP_ERR_ARG, "out is NULL");
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));  // (tgp_qei's rule)
   if (int rc = set_device(h)) return rc;
   const double *dw1, *dw2;
   if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
   // (the time reported is the posterior part, as tgp_qei reports it)
-  return joint_tail_chunks(h, Xq, G, q, chunk, out, 1, where, true, BEI_NOT_PD,
+  return joint_tail_chunks(h, Xq, G, q, joint_group_chunk(q), out, 1, where, true, BEI_NOT_PD,
                            [&](const double* dmean, const double* dcov, int64_t gc, double* dout) {
                              launch_bei_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, dout, h->d_info.as<int>());
                            });
@@ -2603,21 +2688,15 @@ int tgp_batch_ei_moments(tgp_handle h, const double* mean, const double* cov, in
   if (int rc = set_device(h)) return rc;
   const double *dw1, *dw2;
   if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
-  return for_group_chunks(h, G, chunk, true, BEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
-    const double *dmean, *dcov;
-    double* dout;
-    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, (size_t)gc * q, where, &dmean)) return rc;
-    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, (size_t)gc * q * q, where, &dcov)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_out3, out + g0, gc, where, &dout)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // here the events bracket the tail itself
-    launch_bei_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, dout, h->d_info.as<int>());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    return stage_out_finish(h, dout, out + g0, gc, where);
+  MomentArrays m = moment_arrays(h, 1, q, (int64_t)q * q, mean, cov, out);
+  return moments_chunks(h, G, joint_group_chunk(q), BEI_NOT_PD, where, m, [&](int64_t gc, int64_t) {
+    return bracketed(h, [&] {   // (here the events bracket the tail itself)
+      launch_bei_tail(h->stream, m[M_MEAN].dev, m[M_COV].dev, gc, q, dw1, dw2, S, eta, m[M_VAL].dev, h->d_info.as<int>());
+    });
   });
 }
 
-// ---- the analytic batch EI's gradient: bei_grad_tail_kernel on given moments, and tgp_qei_value_grad's body around it ---------------
+// ---- the analytic batch EI's gradient: bei_grad_tail_kernel on given moments (moments_chunks) and behind the posterior (joint_value_grad) ----
 int tgp_batch_ei_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* w1,
                               const double* w2, int S, double eta, double* val, double* gmean, double* gcov, int where) {
   if (!h) return TGP_ERR_ARG;
@@ -2627,24 +2706,13 @@ int tgp_batch_ei_moments_grad(tgp_handle h, const double* mean, const double* co
   if (int rc = set_device(h)) return rc;
   const double *dw1, *dw2;
   if (int rc = bei_stage_points(h, q, w1, w2, S, where, &dw1, &dw2)) return rc;
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)q * q * 8));
-  return for_group_chunks(h, G, chunk, true, BEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
-    // host residency: the moments through s_out1 / s_out2 as in tgp_batch_ei_moments, the value through s_out3, the two
-    // adjoints through s_in and s_ent (idle in a call on given moments: no candidates, no entropy tail)
-    const size_t nm = (size_t)gc * q, nc = (size_t)gc * q * q;
-    const double *dmean, *dcov;
-    double *dval, *dgm, *dgc;
-    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, nm, where, &dmean)) return rc;
-    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, nc, where, &dcov)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_out3, val + g0, (size_t)gc, where, &dval)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_in, gmean + g0 * q, nm, where, &dgm)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_ent, gcov + g0 * q * q, nc, where, &dgc)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // the events bracket the tail itself
-    launch_bei_grad_tail(h->stream, dmean, dcov, gc, q, dw1, dw2, S, eta, 0, dval, dgm, dgc, h->d_info.as<int>());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    if (int rc = stage_out_finish(h, dval, val + g0, (size_t)gc, where)) return rc;
-    if (int rc = stage_out_finish(h, dgm, gmean + g0 * q, nm, where)) return rc;
-    return stage_out_finish(h, dgc, gcov + g0 * q * q, nc, where);
+  MomentArrays m = moment_arrays(h, 1, q, (int64_t)q * q, mean, cov, val, gmean, gcov);
+  // (moments and adjoints of a chunk within 256 MiB each)
+  return moments_chunks(h, G, groups_within(1ull << 28, (int64_t)q * q), BEI_NOT_PD, where, m, [&](int64_t gc, int64_t) {
+    return bracketed(h, [&] {
+      launch_bei_grad_tail(h->stream, m[M_MEAN].dev, m[M_COV].dev, gc, q, dw1, dw2, S, eta, 0, m[M_VAL].dev, m[M_GMEAN].dev,
+                           m[M_GCOV].dev, h->d_info.as<int>());
+    });
   });
 }
 
@@ -2668,25 +2736,22 @@ int tgp_batch_ei_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, co
 int tgp_reparam_samples(tgp_handle h, const double* Xq, int64_t G, int q, const double* eps, int S,
                         double jitter, double* out, int where) {
   if (!h) return TGP_ERR_ARG;
-  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
-  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  if (int rc = check_draws(h, jitter, eps, S)) return rc;
   if (G == 0) return TGP_OK;
   if (!out) return fail(h, TGP_ERR_ARG, "out is NULL");
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)q * std::max(q, S) * 8));
   if (int rc = set_device(h)) return rc;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
-  return joint_tail_chunks(h, Xq, G, q, chunk, out, (size_t)S * q, where, false,
+  return joint_tail_chunks(h, Xq, G, q, samples_group_chunk(q, S), out, (size_t)S * q, where, false,
                            "reparam samples: cov + jitter*I not positive definite for group %lld",
                            [&](const double* dmean, const double* dcov, int64_t gc, double* dout) {
                              launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, 0.0, jitter, nullptr, dout, h->d_info.as<int>());
                            });
 }
 
-// ---- the Monte-Carlo qEI tails on given moments: tgp_batch_ei_moments' / tgp_batch_ei_moments_grad's body around them ------------
+// ---- the Monte-Carlo qEI tails on given moments (moments_chunks) -------------------------------------------------------------------
 static int qei_moments_check(tgp_handle h, int64_t G, int q, const double* eps, int S, double jitter) {
-  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
-  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  if (int rc = check_draws(h, jitter, eps, S)) return rc;
   if (q < 1 || q > MAX_Q) return fail(h, TGP_ERR_SHAPE, "q must be in 1..%d, got %d", MAX_Q, q);
   if (G < 0) return fail(h, TGP_ERR_ARG, "bad arguments");
   return TGP_OK;
@@ -2701,24 +2766,14 @@ int tgp_qei_moments(tgp_handle h, const double* mean, const double* cov, int64_t
   if (int rc = set_device(h)) return rc;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
-  // tgp_qei's chunk rule, with the samples tgp_reparam_samples'
-  const int64_t chunk = samples ? std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)q * std::max(q, S) * 8))
-                                : std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
-  return for_group_chunks(h, G, chunk, true, QEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
-    // host residency: the moments through s_out1 / s_out2, the value through s_out3, the samples through s_ent (idle here)
-    const size_t ns = (size_t)gc * S * q;
-    double* const sam = samples ? samples + g0 * S * q : nullptr;
-    const double *dmean, *dcov;
-    double *dout, *dsam;
-    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, (size_t)gc * q, where, &dmean)) return rc;
-    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, (size_t)gc * q * q, where, &dcov)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_out3, out + g0, (size_t)gc, where, &dout)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_ent, sam, ns, where, &dsam)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // the events bracket the tail itself
-    launch_qei_tail(h->stream, dmean, dcov, gc, q, deps, S, eta, jitter, dout, dsam, h->d_info.as<int>());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    if (int rc = stage_out_finish(h, dsam, sam, ns, where)) return rc;
-    return stage_out_finish(h, dout, out + g0, (size_t)gc, where);
+  MomentArrays m = moment_arrays(h, 1, q, (int64_t)q * q, mean, cov, out);
+  m[M_SAMPLES] = {samples, false, &h->s_ent, 1, (int64_t)S * q, nullptr};   // optional, [G][S][q]
+  const int64_t chunk = samples ? samples_group_chunk(q, S) : joint_group_chunk(q);   // tgp_qei's rule; tgp_reparam_samples' with samples
+  return moments_chunks(h, G, chunk, QEI_NOT_PD, where, m, [&](int64_t gc, int64_t) {
+    return bracketed(h, [&] {
+      launch_qei_tail(h->stream, m[M_MEAN].dev, m[M_COV].dev, gc, q, deps, S, eta, jitter, m[M_VAL].dev, m[M_SAMPLES].dev,
+                      h->d_info.as<int>());
+    });
   });
 }
 
@@ -2726,30 +2781,18 @@ int tgp_qei_moments_grad(tgp_handle h, const double* mean, const double* cov, in
                          double eta, double jitter, double* val, double* gmean, double* gcov, int where) {
   if (!h) return TGP_ERR_ARG;
   if (int rc = qei_moments_check(h, G, q, eps, S, jitter)) return rc;
-  if (qei_grad_tail_lds_bytes(q, S) > (size_t)160 * 1024)   // (tgp_qei_value_grad's refusal)
-    return fail(h, TGP_ERR_SHAPE, "q = %d with S = %d draws does not fit the tail's LDS", q, S);
+  if (!qei_grad_tail_fits(q, S)) return fail(h, TGP_ERR_SHAPE, "q = %d with S = %d draws does not fit the tail's LDS", q, S);
   if (G == 0) return TGP_OK;
   if (!mean || !cov || !val || !gmean || !gcov) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (int rc = set_device(h)) return rc;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)q * S, where, &deps)) return rc;
-  const int64_t chunk = std::max<int64_t>(1, (int64_t)(1ull << 30) / ((int64_t)q * q * 8));
-  return for_group_chunks(h, G, chunk, true, QEI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
-    // host residency as in tgp_batch_ei_moments_grad: the two adjoints through s_in and s_ent
-    const size_t nm = (size_t)gc * q, nc = (size_t)gc * q * q;
-    const double *dmean, *dcov;
-    double *dval, *dgm, *dgc;
-    if (int rc = stage_in(h, h->s_out1, mean + g0 * q, nm, where, &dmean)) return rc;
-    if (int rc = stage_in(h, h->s_out2, cov + g0 * q * q, nc, where, &dcov)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_out3, val + g0, (size_t)gc, where, &dval)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_in, gmean + g0 * q, nm, where, &dgm)) return rc;
-    if (int rc = stage_out_prepare(h, h->s_ent, gcov + g0 * q * q, nc, where, &dgc)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));   // the events bracket the tail itself
-    launch_qei_grad_tail(h->stream, dmean, dcov, gc, q, deps, S, eta, jitter, dval, dgm, dgc, h->d_info.as<int>());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    if (int rc = stage_out_finish(h, dval, val + g0, (size_t)gc, where)) return rc;
-    if (int rc = stage_out_finish(h, dgm, gmean + g0 * q, nm, where)) return rc;
-    return stage_out_finish(h, dgc, gcov + g0 * q * q, nc, where);
+  MomentArrays m = moment_arrays(h, 1, q, (int64_t)q * q, mean, cov, val, gmean, gcov);
+  return moments_chunks(h, G, joint_group_chunk(q), QEI_NOT_PD, where, m, [&](int64_t gc, int64_t) {
+    return bracketed(h, [&] {
+      launch_qei_grad_tail(h->stream, m[M_MEAN].dev, m[M_COV].dev, gc, q, deps, S, eta, jitter, m[M_VAL].dev, m[M_GMEAN].dev,
+                           m[M_GCOV].dev, h->d_info.as<int>());
+    });
   });
 }
 
@@ -3292,15 +3335,6 @@ PartitionDev partition_dev(tgp_handle h) {
   return {db, (const uint32_t*)(db + (size_t)h->ehvi_P * h->ehvi_V), h->ehvi_P, h->ehvi_V, h->ehvi_K, h->ehvi_nb};
 }
 
-// a launch on the handle's stream between its two events (ehvi_read_tail_ms and for_group_chunks read them): enqueue only
-template <class Launch>
-int bracketed(tgp_handle h, Launch launch) {
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  launch();
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  return TGP_OK;
-}
-
 // a member's status as the call's: the error belongs to the leading handle
 int member_rc(tgp_handle h, tgp_handle t, int rc) {
   if (rc && t != h) h->err = t->err;
@@ -3461,13 +3495,11 @@ int tgp_ehvi_moments(tgp_handle h, const double* mean, const double* var, int64_
   if (M == 0) return TGP_OK;
   if (!mean || !var || !out) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (int rc = set_device(h)) return rc;
-  const double *dmean, *dvar;
-  double* dout;
-  if (int rc = stage_in(h, h->s_out1, mean, (size_t)h->ehvi_P * M, where, &dmean)) return rc;
-  if (int rc = stage_in(h, h->s_out2, var, (size_t)h->ehvi_P * M, where, &dvar)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out3, out, M, where, &dout)) return rc;
-  if (int rc = ehvi_enqueue_tail(h, dmean, dvar, M, dout)) return rc;
-  if (int rc = stage_out_finish(h, dout, out, M, where)) return rc;
+  // (one chunk of M groups of one double: no chunk loop, which would zero and read d_info)
+  MomentArrays m = moment_arrays(h, h->ehvi_P, 1, 1, mean, var, out);
+  if (int rc = stage_chunk(h, m, 0, M, M, where, true)) return rc;
+  if (int rc = ehvi_enqueue_tail(h, m[M_MEAN].dev, m[M_COV].dev, M, m[M_VAL].dev)) return rc;
+  if (int rc = stage_chunk(h, m, 0, M, M, where, false)) return rc;
   if (int rc = finish(h)) return rc;
   ehvi_read_tail_ms(h);
   h->ehvi_sweep_ms = 0.0;
@@ -3525,20 +3557,10 @@ int tgp_ehvi_moments_grad(tgp_handle h, const double* mean, const double* var, i
   if (M == 0) return TGP_OK;
   if (!mean || !var || !val || !gmean || !gvar) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (int rc = set_device(h)) return rc;
-  // host residency: the moments through s_out1 / s_out2 as in tgp_ehvi_moments, the value through s_out3, the two adjoints
-  // through s_in and s_ent (idle in a call on given moments)
-  const size_t pm = (size_t)h->ehvi_P * M;
-  const double *dmean, *dvar;
-  double *dval, *dgm, *dgv;
-  if (int rc = stage_in(h, h->s_out1, mean, pm, where, &dmean)) return rc;
-  if (int rc = stage_in(h, h->s_out2, var, pm, where, &dvar)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_out3, val, M, where, &dval)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_in, gmean, pm, where, &dgm)) return rc;
-  if (int rc = stage_out_prepare(h, h->s_ent, gvar, pm, where, &dgv)) return rc;
-  if (int rc = ehvi_enqueue_grad_tail(h, dmean, dvar, M, 0, dval, dgm, dgv)) return rc;
-  if (int rc = stage_out_finish(h, dval, val, M, where)) return rc;
-  if (int rc = stage_out_finish(h, dgm, gmean, pm, where)) return rc;
-  if (int rc = stage_out_finish(h, dgv, gvar, pm, where)) return rc;
+  MomentArrays m = moment_arrays(h, h->ehvi_P, 1, 1, mean, var, val, gmean, gvar);   // (one chunk, no chunk loop)
+  if (int rc = stage_chunk(h, m, 0, M, M, where, true)) return rc;
+  if (int rc = ehvi_enqueue_grad_tail(h, m[M_MEAN].dev, m[M_COV].dev, M, 0, m[M_VAL].dev, m[M_GMEAN].dev, m[M_GCOV].dev)) return rc;
+  if (int rc = stage_chunk(h, m, 0, M, M, where, false)) return rc;
   if (int rc = finish(h)) return rc;
   ehvi_read_tail_ms(h);
   h->ehvi_sweep_ms = 0.0;
@@ -3582,15 +3604,9 @@ constexpr const char* QEHVI_NOT_PD ="qEHVI: a covariance of group %lld is not po
 
 int qehvi_check(tgp_handle h, int64_t G, int q, const double* eps, int S, double jitter) {
   if (q < 1 || q > QEHVI_MAX_Q) return fail(h, TGP_ERR_SHAPE, "qEHVI: q must be in 1..%d, got %d", QEHVI_MAX_Q, q);
-  if (!(jitter >= 0.0)) return fail(h, TGP_ERR_ARG, "jitter must be >= 0");
-  if (S < 1 || !eps) return fail(h, TGP_ERR_ARG, "need S >= 1 draws");
+  if (int rc = check_draws(h, jitter, eps, S)) return rc;
   if (G < 0) return fail(h, TGP_ERR_SHAPE, "G must be >= 0");
   return TGP_OK;
-}
-
-// groups per chunk: the chunk's moments, 8 P (q + q^2) bytes per group, stay within 256 MiB
-int64_t qehvi_group_chunk(int P, int q) {
-  return std::max<int64_t>(1, (int64_t)(1ull << 28) / ((int64_t)8 * P * q * (q + 1)));
 }
 
 // the tail on device-resident moments of `gc` groups (objective stride `gstride` groups), bracketed by the handle's events
@@ -3613,20 +3629,6 @@ int qehvi_enqueue_grad_tail(tgp_handle h, const double* dmean, const double* dco
   });
 }
 
-// host [P][G][n] -> buf [P][gc][n]: the groups g0 .. g0 + gc of every objective behind each other (enqueue only); and back
-int gather_stack_chunk(tgp_handle h, DevBuf& buf, const double* host, int P, int64_t G, int64_t g0, int64_t gc, int64_t n) {
-  for (int j = 0; j < P; ++j)
-    HIPCHK(h, hipMemcpyAsync(buf.as<double>() + (size_t)j * gc * n, host + ((int64_t)j * G + g0) * n,
-                             (size_t)gc * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  return TGP_OK;
-}
-int scatter_stack_chunk(tgp_handle h, double* host, const double* dev, int P, int64_t G, int64_t g0, int64_t gc, int64_t n) {
-  for (int j = 0; j < P; ++j)
-    HIPCHK(h, hipMemcpyAsync(host + ((int64_t)j * G + g0) * n, dev + (size_t)j * gc * n, (size_t)gc * n * sizeof(double),
-                             hipMemcpyDeviceToHost, h->stream));
-  return TGP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -3640,25 +3642,11 @@ int tgp_qehvi_moments(tgp_handle h, const double* mean, const double* cov, int64
   if (!mean || !cov || !out) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (int rc = set_device(h)) return rc;
   const int P = h->ehvi_P;
-  const int64_t qq = (int64_t)q * q;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)P * q * S, where, &deps)) return rc;
-  const int rc = for_group_chunks(h, G, qehvi_group_chunk(P, q), true, QEHVI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
-    const double *dmean = mean + g0 * q, *dcov = cov + g0 * qq;
-    int64_t gstride = G;
-    double* dout;
-    if (where != TGP_DEVICE) {   // objective j's groups of this chunk behind each other: [P][gc]
-      HIPCHK(h, h->s_out1.reserve((size_t)P * gc * q * sizeof(double)));
-      HIPCHK(h, h->s_out2.reserve((size_t)P * gc * qq * sizeof(double)));
-      if (int rb = gather_stack_chunk(h, h->s_out1, mean, P, G, g0, gc, q)) return rb;
-      if (int rb = gather_stack_chunk(h, h->s_out2, cov, P, G, g0, gc, qq)) return rb;
-      dmean = h->s_out1.as<double>();
-      dcov = h->s_out2.as<double>();
-      gstride = gc;
-    }
-    if (int rb = stage_out_prepare(h, h->s_out3, out + g0, (size_t)gc, where, &dout)) return rb;
-    if (int rb = qehvi_enqueue_tail(h, dmean, dcov, gc, gstride, q, deps, S, jitter, dout)) return rb;
-    return stage_out_finish(h, dout, out + g0, (size_t)gc, where);
+  MomentArrays m = moment_arrays(h, P, q, (int64_t)q * q, mean, cov, out);
+  const int rc = moments_chunks(h, G, qehvi_group_chunk(P, q), QEHVI_NOT_PD, where, m, [&](int64_t gc, int64_t gstride) {
+    return qehvi_enqueue_tail(h, m[M_MEAN].dev, m[M_COV].dev, gc, gstride, q, deps, S, jitter, m[M_VAL].dev);
   });
   h->ehvi_sweep_ms = 0.0;
   h->ehvi_tail_ms = h->last_ms;
@@ -3718,37 +3706,14 @@ int tgp_qehvi_moments_grad(tgp_handle h, const double* mean, const double* cov, 
   if (!mean || !cov || !val || !gmean || !gcov) return fail(h, TGP_ERR_ARG, "bad arguments");
   if (int rc = set_device(h)) return rc;
   const int P = h->ehvi_P;
-  const int64_t qq = (int64_t)q * q;
   const double* deps;
   if (int rc = stage_in(h, h->s_in2, eps, (size_t)P * q * S, where, &deps)) return rc;
+  MomentArrays m = moment_arrays(h, P, q, (int64_t)q * q, mean, cov, val, gmean, gcov);
   // (moments and adjoints of a chunk within 256 MiB: half of tgp_qehvi_moments' groups)
   const int64_t chunk = std::max<int64_t>(1, qehvi_group_chunk(P, q) / 2);
-  const int rc = for_group_chunks(h, G, chunk, true, QEHVI_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
-    // host residency: the moments through s_out1 / s_out2 as in tgp_qehvi_moments, the value through s_out3, the two adjoints
-    // through s_in and s_ent (idle in a call on given moments), objective j's groups of this chunk behind each other: [P][gc]
-    const double *dmean = mean + g0 * q, *dcov = cov + g0 * qq;
-    double *dval, *dgm = gmean + g0 * q, *dgc = gcov + g0 * qq;
-    int64_t gstride = G;
-    if (where != TGP_DEVICE) {
-      HIPCHK(h, h->s_out1.reserve((size_t)P * gc * q * sizeof(double)));
-      HIPCHK(h, h->s_out2.reserve((size_t)P * gc * qq * sizeof(double)));
-      HIPCHK(h, h->s_in.reserve((size_t)P * gc * q * sizeof(double)));
-      HIPCHK(h, h->s_ent.reserve((size_t)P * gc * qq * sizeof(double)));
-      if (int rb = gather_stack_chunk(h, h->s_out1, mean, P, G, g0, gc, q)) return rb;
-      if (int rb = gather_stack_chunk(h, h->s_out2, cov, P, G, g0, gc, qq)) return rb;
-      dmean = h->s_out1.as<double>();
-      dcov = h->s_out2.as<double>();
-      dgm = h->s_in.as<double>();
-      dgc = h->s_ent.as<double>();
-      gstride = gc;
-    }
-    if (int rb = stage_out_prepare(h, h->s_out3, val + g0, (size_t)gc, where, &dval)) return rb;
-    if (int rb = qehvi_enqueue_grad_tail(h, dmean, dcov, gc, gstride, q, deps, S, jitter, 0, dval, dgm, dgc)) return rb;
-    if (where != TGP_DEVICE) {
-      if (int rb = scatter_stack_chunk(h, gmean, dgm, P, G, g0, gc, q)) return rb;
-      if (int rb = scatter_stack_chunk(h, gcov, dgc, P, G, g0, gc, qq)) return rb;
-    }
-    return stage_out_finish(h, dval, val + g0, (size_t)gc, where);
+  const int rc = moments_chunks(h, G, chunk, QEHVI_NOT_PD, where, m, [&](int64_t gc, int64_t gstride) {
+    return qehvi_enqueue_grad_tail(h, m[M_MEAN].dev, m[M_COV].dev, gc, gstride, q, deps, S, jitter, 0, m[M_VAL].dev, m[M_GMEAN].dev,
+                                   m[M_GCOV].dev);
   });
   h->ehvi_sweep_ms = 0.0;
   h->ehvi_tail_ms = h->last_ms;

@@ -40,6 +40,61 @@ class _Arg:
         self.shape, self.device = a.shape, None
 
 
+# -- one parser per kind of argument ------------------------------------------------------------------------------------
+def _groups(lead) -> int:
+    return int(np.prod(lead)) if lead else 1
+
+
+def _batch_points(d: int, Xq, noun: str = "batch"):
+    """Xq [..., q, d] -> (argument, leading shape, q, number of q-batches)."""
+    a = _Arg(Xq)
+    if len(a.shape) < 2 or a.shape[-1] != d:
+        raise ValueError(f"{noun} query points must be [..., q, {d}], got {a.shape}")
+    lead, q = a.shape[:-2], a.shape[-2]
+    return a, lead, q, _groups(lead)
+
+
+def _draws(a: _Arg, q: int, eps) -> _Arg:
+    """eps [q, S], where the points ``a`` live."""
+    e = _Arg(eps)
+    if len(e.shape) != 2 or e.shape[0] != q:
+        raise ValueError(f"eps must be [q={q}, S], got {e.shape}")
+    if e.where != a.where:
+        raise ValueError("Xq and eps must live in the same place (both host or both device)")
+    return e
+
+
+_MOMENT_FORMS = {"...": (1, False), "G": (2, True), "P, ...": (2, False)}   # leading axes -> (lowest rank of mean, exactly that)
+
+
+def _moment_pair(mean, cov, form: str, same_place: bool = True):
+    """mean [<form>, q] and cov [<form>, q, q] as a model's ``predict_joint`` returns them -> the two arguments."""
+    m, c = _Arg(mean), _Arg(cov)
+    low, exact = _MOMENT_FORMS[form]
+    if len(m.shape) < low or (exact and len(m.shape) != low) or c.shape != m.shape + (m.shape[-1],):
+        raise ValueError(f"mean must be [{form}, q] and cov [{form}, q, q], got {m.shape} and {c.shape}")
+    if same_place and m.where != c.where:
+        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    return m, c
+
+
+def _marginal_pair(mean, var):
+    """mean, var [P, M] objective-major -> the two arguments."""
+    m, v = _Arg(mean), _Arg(var)
+    if len(m.shape) != 2 or m.shape != v.shape:
+        raise ValueError(f"mean and var must both be [P, M], got {m.shape} and {v.shape}")
+    if m.where != v.where:
+        raise ValueError("mean and var must live in the same place (both host or both device)")
+    return m, v
+
+
+def _value_grad_outputs(m: _Arg, lead, second_shape):
+    """The outputs of a tail with its adjoints where the moments live: value [lead], the mean's adjoint in the mean's shape, the
+    second moment's in ``second_shape`` -> ((value, gmean, gsecond), their three pointers)."""
+    outs = [GPEngine._out(m, shape) for shape in (lead, m.shape, second_shape)]
+    return tuple(o[0] for o in outs), tuple(o[1] for o in outs)
+
+
 class GPEngine:
     def __init__(self, d: int, kernel: str = "matern52", device: int = 0):
         """An exact-GPR engine on ``device`` for inputs of ``d`` dimensions, 1 <= d <= 1024 (``_lib.MAX_D``).  Above 32
@@ -335,7 +390,7 @@ class GPEngine:
         if len(a.shape) < 1 or a.shape[-1] != self.d:
             raise ValueError(f"query points must have trailing dimension {self.d}, got {a.shape}")
         lead = a.shape[:-1]
-        return a, lead, int(np.prod(lead)) if lead else 1
+        return a, lead, _groups(lead)
 
     def predict(self, Xq):
         a, lead, M = self._flat(Xq)
@@ -351,11 +406,7 @@ class GPEngine:
         return mean
 
     def predict_joint(self, Xq):
-        a = _Arg(Xq)
-        if len(a.shape) < 2 or a.shape[-1] != self.d:
-            raise ValueError(f"joint query points must be [..., q, {self.d}], got {a.shape}")
-        lead, q = a.shape[:-2], a.shape[-2]
-        G = int(np.prod(lead)) if lead else 1
+        a, lead, q, G = _batch_points(self.d, Xq, "joint")
         mean, pm = self._out(a, lead + (q,))
         cov, pc = self._out(a, lead + (q, q))
         self._chk(self._lib.tgp_predict_joint(self._h, a.ptr, G, q, pm, pc, a.where))
@@ -465,16 +516,8 @@ class GPEngine:
         return out
 
     def qei(self, Xq, eps, eta: float, jitter: float = 1e-6):
-        a = _Arg(Xq)
-        if len(a.shape) < 2 or a.shape[-1] != self.d:
-            raise ValueError(f"batch query points must be [..., q, {self.d}], got {a.shape}")
-        lead, q = a.shape[:-2], a.shape[-2]
-        G = int(np.prod(lead)) if lead else 1
-        e = _Arg(eps)
-        if len(e.shape) != 2 or e.shape[0] != q:
-            raise ValueError(f"eps must be [q={q}, S], got {e.shape}")
-        if e.where != a.where:
-            raise ValueError("Xq and eps must live in the same place (both host or both device)")
+        a, lead, q, G = _batch_points(self.d, Xq)
+        e = _draws(a, q, eps)
         out, po = self._out(a, lead)
         self._chk(self._lib.tgp_qei(self._h, a.ptr, G, q, e.ptr, e.shape[1], float(eta), float(jitter), po,
                                     a.where))
@@ -524,11 +567,7 @@ class GPEngine:
         """Xq [G, q, d] (G * q <= 2048, q <= 64), eps [q, S] -> (qEI [G], gradient [G, q, d]) in one device call
         (tgp_qei_value_grad)."""
         a, G, q = self._joint_small(Xq)
-        e = _Arg(eps)
-        if len(e.shape) != 2 or e.shape[0] != q:
-            raise ValueError(f"eps must be [q={q}, S], got {e.shape}")
-        if e.where != a.where:
-            raise ValueError("Xq and eps must live in the same place (both host or both device)")
+        e = _draws(a, q, eps)
         val, pv = self._out(a, (G,))
         grad, pg = self._out(a, (G, q, self.d))
         if G:
@@ -538,16 +577,8 @@ class GPEngine:
 
     def reparam_samples(self, Xq, eps, jitter: float = 1e-6):
         """Xq [..., q, d], eps [q, S] -> samples [..., S, q]."""
-        a = _Arg(Xq)
-        if len(a.shape) < 2 or a.shape[-1] != self.d:
-            raise ValueError(f"batch query points must be [..., q, {self.d}], got {a.shape}")
-        lead, q = a.shape[:-2], a.shape[-2]
-        G = int(np.prod(lead)) if lead else 1
-        e = _Arg(eps)
-        if len(e.shape) != 2 or e.shape[0] != q:
-            raise ValueError(f"eps must be [q={q}, S], got {e.shape}")
-        if e.where != a.where:
-            raise ValueError("Xq and eps must live in the same place (both host or both device)")
+        a, lead, q, G = _batch_points(self.d, Xq)
+        e = _draws(a, q, eps)
         S = e.shape[1]
         out, po = self._out(a, lead + (S, q))
         self._chk(self._lib.tgp_reparam_samples(self._h, a.ptr, G, q, e.ptr, S, float(jitter), po, a.where))
@@ -751,19 +782,19 @@ def _sobol_args(a: _Arg, q: int, w1, w2):
     return p1, p2, S
 
 
+def _check_bei_q(q: int) -> None:
+    if not 2 <= q <= BATCH_EI_MAX_Q:
+        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
+
+
 def batch_ei(engine, Xq, w1, w2, eta: float):
     """Xq [..., q, d] (2 <= q <= 16), Sobol points w1 [S, q] and w2 [S, q - 1] in [0, 1) -> [...]: the analytic multi-point
     expected improvement of every q-batch (reference ``batch_expected_improvement.__call__``), posterior and tail on the
     device (tgp_batch_ei).  Value only."""
     if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei"):
         return engine.batch_ei(Xq, w1, w2, eta)
-    a = _Arg(Xq)
-    if len(a.shape) < 2 or a.shape[-1] != engine.d:
-        raise ValueError(f"batch query points must be [..., q, {engine.d}], got {a.shape}")
-    lead, q = a.shape[:-2], a.shape[-2]
-    if not 2 <= q <= BATCH_EI_MAX_Q:
-        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
-    G = int(np.prod(lead)) if lead else 1
+    a, lead, q, G = _batch_points(engine.d, Xq)
+    _check_bei_q(q)
     p1, p2, S = _sobol_args(a, q, w1, w2)
     out, po = GPEngine._out(a, lead)
     engine._chk(engine._lib.tgp_batch_ei(engine._h, a.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), po, a.where))
@@ -776,18 +807,13 @@ def batch_ei_moments(engine, mean, cov, w1, w2, eta: float):
     change of sign of ``__call__``).  Needs no data on the engine."""
     if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei_moments"):
         return engine.batch_ei_moments(mean, cov, w1, w2, eta)
-    m, c = _Arg(mean), _Arg(cov)
-    if len(m.shape) < 1 or c.shape != m.shape + (m.shape[-1],):
-        raise ValueError(f"mean must be [..., q] and cov [..., q, q], got {m.shape} and {c.shape}")
-    if m.where != c.where:
-        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    m, c = _moment_pair(mean, cov, "...")
     lead, q = m.shape[:-1], m.shape[-1]
-    if not 2 <= q <= BATCH_EI_MAX_Q:
-        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
-    G = int(np.prod(lead)) if lead else 1
+    _check_bei_q(q)
     p1, p2, S = _sobol_args(m, q, w1, w2)
     out, po = GPEngine._out(m, lead)
-    engine._chk(engine._lib.tgp_batch_ei_moments(engine._h, m.ptr, c.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), po, m.where))
+    engine._chk(engine._lib.tgp_batch_ei_moments(engine._h, m.ptr, c.ptr, _groups(lead), q, p1.ptr, p2.ptr, S, float(eta), po,
+                                                 m.where))
     return out
 
 
@@ -797,27 +823,17 @@ def batch_ei_moments_grad(engine, mean, cov, w1, w2, eta: float):
     Needs no data on the engine."""
     if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei_moments_grad"):
         return engine.batch_ei_moments_grad(mean, cov, w1, w2, eta)
-    m, c = _Arg(mean), _Arg(cov)
-    if len(m.shape) != 2 or c.shape != m.shape + (m.shape[-1],):
-        raise ValueError(f"mean must be [G, q] and cov [G, q, q], got {m.shape} and {c.shape}")
-    if m.where != c.where:
-        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    m, c = _moment_pair(mean, cov, "G")
     G, q = m.shape
-    if not 2 <= q <= BATCH_EI_MAX_Q:
-        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
+    _check_bei_q(q)
     p1, p2, S = _sobol_args(m, q, w1, w2)
-    val, pv = GPEngine._out(m, (G,))
-    gm, pgm = GPEngine._out(m, (G, q))
-    gc, pgc = GPEngine._out(m, (G, q, q))
-    engine._chk(engine._lib.tgp_batch_ei_moments_grad(engine._h, m.ptr, c.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), pv, pgm,
-                                                      pgc, m.where))
-    return val, gm, gc
+    outs, ptrs = _value_grad_outputs(m, (G,), c.shape)
+    engine._chk(engine._lib.tgp_batch_ei_moments_grad(engine._h, m.ptr, c.ptr, G, q, p1.ptr, p2.ptr, S, float(eta), *ptrs, m.where))
+    return outs
 
 
 def _qei_moment_args(mean, cov, eps):
-    m, c, e = _Arg(mean), _Arg(cov), _Arg(eps)
-    if len(m.shape) != 2 or c.shape != m.shape + (m.shape[-1],):
-        raise ValueError(f"mean must be [G, q] and cov [G, q, q], got {m.shape} and {c.shape}")
+    (m, c), e = _moment_pair(mean, cov, "G", same_place=False), _Arg(eps)
     G, q = m.shape
     if not 1 <= q <= 64:
         raise ValueError(f"the Monte-Carlo qEI takes 1 <= q <= 64 points per batch, got {q}")
@@ -844,12 +860,9 @@ def qei_moments_grad(engine, mean, cov, eps, eta: float, jitter: float = 1e-6):
     d value = sum gcov * dcov for every symmetric dcov (tgp_qei_moments_grad); (q, S) within ``GPEngine.qei_value_grad_fits``.
     Needs no data on the engine."""
     m, c, e, G, q, S = _qei_moment_args(mean, cov, eps)
-    val, pv = GPEngine._out(m, (G,))
-    gm, pgm = GPEngine._out(m, (G, q))
-    gc, pgc = GPEngine._out(m, (G, q, q))
-    engine._chk(engine._lib.tgp_qei_moments_grad(engine._h, m.ptr, c.ptr, G, q, e.ptr, S, float(eta), float(jitter), pv, pgm, pgc,
-                                                 m.where))
-    return val, gm, gc
+    outs, ptrs = _value_grad_outputs(m, (G,), c.shape)
+    engine._chk(engine._lib.tgp_qei_moments_grad(engine._h, m.ptr, c.ptr, G, q, e.ptr, S, float(eta), float(jitter), *ptrs, m.where))
+    return outs
 
 
 def batch_ei_value_grad(engine, Xq, w1, w2, eta: float):
@@ -859,8 +872,7 @@ def batch_ei_value_grad(engine, Xq, w1, w2, eta: float):
     if not isinstance(engine, GPEngine) and hasattr(engine, "batch_ei_value_grad"):
         return engine.batch_ei_value_grad(Xq, w1, w2, eta)
     a, G, q = engine._joint_small(Xq)
-    if not 2 <= q <= BATCH_EI_MAX_Q:
-        raise ValueError(f"the analytic batch EI takes 2 <= q <= {BATCH_EI_MAX_Q} points per batch, got {q}")
+    _check_bei_q(q)
     p1, p2, S = _sobol_args(a, q, w1, w2)
     val, pv = GPEngine._out(a, (G,))
     grad, pg = GPEngine._out(a, (G, q, engine.d))
@@ -931,11 +943,7 @@ def ehvi_set_partition(engine, lower, upper) -> None:
 def ehvi_moments(engine, mean, var):
     """The EHVI tail on caller-supplied moments: mean, var [P, M] objective-major (host arrays or CUDA tensors) -> [M]
     (tgp_ehvi_moments).  Needs a partition on the engine and no data."""
-    m, v = _Arg(mean), _Arg(var)
-    if len(m.shape) != 2 or m.shape != v.shape:
-        raise ValueError(f"mean and var must both be [P, M], got {m.shape} and {v.shape}")
-    if m.where != v.where:
-        raise ValueError("mean and var must live in the same place (both host or both device)")
+    m, v = _marginal_pair(mean, var)
     out, po = GPEngine._out(m, (m.shape[1],))
     engine._chk(engine._lib.tgp_ehvi_moments(engine._h, m.ptr, v.ptr, int(m.shape[1]), po, m.where))
     return out
@@ -984,16 +992,10 @@ def ehvi_grad_tile_width(P: int, V: int) -> int:
 def ehvi_moments_grad(engine, mean, var):
     """The EHVI tail with the adjoints of the moments on caller-supplied moments: mean, var [P, M] objective-major ->
     (value [M], gmean [P, M], gvar [P, M]) (tgp_ehvi_moments_grad).  Needs a partition on the engine and no data."""
-    m, v = _Arg(mean), _Arg(var)
-    if len(m.shape) != 2 or m.shape != v.shape:
-        raise ValueError(f"mean and var must both be [P, M], got {m.shape} and {v.shape}")
-    if m.where != v.where:
-        raise ValueError("mean and var must live in the same place (both host or both device)")
-    val, pv = GPEngine._out(m, (m.shape[1],))
-    gm, pgm = GPEngine._out(m, m.shape)
-    gv, pgv = GPEngine._out(m, m.shape)
-    engine._chk(engine._lib.tgp_ehvi_moments_grad(engine._h, m.ptr, v.ptr, int(m.shape[1]), pv, pgm, pgv, m.where))
-    return val, gm, gv
+    m, v = _marginal_pair(mean, var)
+    outs, ptrs = _value_grad_outputs(m, (m.shape[1],), v.shape)
+    engine._chk(engine._lib.tgp_ehvi_moments_grad(engine._h, m.ptr, v.ptr, int(m.shape[1]), *ptrs, m.where))
+    return outs
 
 
 def ehvi_value_grad(engines, Xq):
@@ -1048,16 +1050,12 @@ def _qehvi_eps(P: int, q: int, eps, where):
 def qehvi_moments(engine, mean, cov, eps, jitter: float = 1e-6):
     """The qEHVI tail on caller-supplied joint moments as the models return them: mean [P, ..., q], cov [P, ..., q, q]
     objective-major, eps [P, q, S] -> [...] (tgp_qehvi_moments).  Needs a partition on the engine and no data."""
-    m, c = _Arg(mean), _Arg(cov)
-    if len(m.shape) < 2 or c.shape != m.shape + (m.shape[-1],):
-        raise ValueError(f"mean must be [P, ..., q] and cov [P, ..., q, q], got {m.shape} and {c.shape}")
-    if m.where != c.where:
-        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    m, c = _moment_pair(mean, cov, "P, ...")
     P, lead, q = m.shape[0], m.shape[1:-1], m.shape[-1]
-    G = int(np.prod(lead)) if lead else 1
     e = _qehvi_eps(P, q, eps, m.where)
     out, po = GPEngine._out(m, lead)
-    engine._chk(engine._lib.tgp_qehvi_moments(engine._h, m.ptr, c.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter), po, m.where))
+    engine._chk(engine._lib.tgp_qehvi_moments(engine._h, m.ptr, c.ptr, _groups(lead), q, e.ptr, int(e.shape[2]), float(jitter), po,
+                                              m.where))
     return out
 
 
@@ -1065,11 +1063,7 @@ def qehvi_values(engines, Xq, eps, jitter: float = 1e-6):
     """engines: one :class:`GPEngine` per objective (the first carries the partition); Xq [..., q, d], eps [P, q, S] ->
     qEHVI [...]: every engine's ``predict_joint`` and the tail in one device call (tgp_qehvi_values)."""
     engines, hs = _handles(engines)
-    a = _Arg(Xq)
-    if len(a.shape) < 2 or a.shape[-1] != engines[0].d:
-        raise ValueError(f"batch query points must be [..., q, {engines[0].d}], got {a.shape}")
-    lead, q = a.shape[:-2], a.shape[-2]
-    G = int(np.prod(lead)) if lead else 1
+    a, lead, q, G = _batch_points(engines[0].d, Xq)
     e = _qehvi_eps(len(engines), q, eps, a.where)
     out, po = GPEngine._out(a, lead)
     engines[0]._chk(engines[0]._lib.tgp_qehvi_values(hs, len(engines), a.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter), po,
@@ -1102,20 +1096,13 @@ def qehvi_moments_grad(engine, mean, cov, eps, jitter: float = 1e-6):
     """The qEHVI tail with the adjoints of the joint moments on caller-supplied moments: mean [P, ..., q], cov [P, ..., q, q]
     objective-major, eps [P, q, S] -> (value [...], gmean [P, ..., q], gcov [P, ..., q, q] symmetric)
     (tgp_qehvi_moments_grad).  The value is :func:`qehvi_moments`' bit for bit.  Needs a partition and no data."""
-    m, c = _Arg(mean), _Arg(cov)
-    if len(m.shape) < 2 or c.shape != m.shape + (m.shape[-1],):
-        raise ValueError(f"mean must be [P, ..., q] and cov [P, ..., q, q], got {m.shape} and {c.shape}")
-    if m.where != c.where:
-        raise ValueError("mean and cov must live in the same place (both host or both device)")
+    m, c = _moment_pair(mean, cov, "P, ...")
     P, lead, q = m.shape[0], m.shape[1:-1], m.shape[-1]
-    G = int(np.prod(lead)) if lead else 1
     e = _qehvi_eps(P, q, eps, m.where)
-    val, pv = GPEngine._out(m, lead)
-    gm, pgm = GPEngine._out(m, m.shape)
-    gc, pgc = GPEngine._out(m, c.shape)
-    engine._chk(engine._lib.tgp_qehvi_moments_grad(engine._h, m.ptr, c.ptr, G, q, e.ptr, int(e.shape[2]), float(jitter), pv, pgm,
-                                                   pgc, m.where))
-    return val, gm, gc
+    outs, ptrs = _value_grad_outputs(m, lead, c.shape)
+    engine._chk(engine._lib.tgp_qehvi_moments_grad(engine._h, m.ptr, c.ptr, _groups(lead), q, e.ptr, int(e.shape[2]), float(jitter),
+                                                   *ptrs, m.where))
+    return outs
 
 
 def qehvi_value_grad(engines, Xq, eps, jitter: float = 1e-6):
