@@ -446,6 +446,39 @@ int tgp_qei_moments(tgp_handle h, const double* mean, const double* cov, int64_t
 int tgp_qei_moments_grad(tgp_handle h, const double* mean, const double* cov, int64_t G, int q, const double* eps, int S,
                          double eta, double jitter, double* val, double* gmean, double* gcov, int where);
 
+/* == IntegratedVarianceReduction / integrated_variance_reduction (acquisition/function/active_learning.py:250-415): how much the
+ * predictive variance, averaged with weights over P integration points Z, drops when a batch of q points is observed.  The
+ * reference computes conditional_predict_f(Z, additional_data = x) per batch (models/gpflow/models.py:355-416); here the
+ * conditioned variance is the Schur complement over the q new points,
+ *     v_new(z) = v_old(z) - c_z^T (Sigma_xx + s^2 I)^-1 c_z,   c_z = cov(x, z) = k(x, z) - (W k(X, x))^T (W k(X, z))   (models.py:379-394),
+ * Sigma_xx = tgp_predict_joint's covariance (diagonal clipped at 1e-12), s^2 the likelihood noise, no jitter (models.py:390-394).
+ *   tgp_set_integration_points: handle state, like tgp_set_min_value_samples.  Z [P,d], weights [P] or NULL (all ones), both host
+ *     or both device by `where`; the handle keeps its own copies.  P = 0 clears the setting; 1 <= P <= TGP_IVR_MAX_P else
+ *     TGP_ERR_SHAPE (the cap bounds the scratch: C_Z = W k(X, Z) is 512 MiB at N = 4096, a 2048-point chunk of the cross product
+ *     256 MiB); a weight that is negative or not finite is TGP_ERR_ARG.  What depends on the model -- C_Z, Z / lengthscales, and
+ *     c0 = (1/P) sum_z w_z var_old(z) with var_old tgp_predict's clipped variance -- is built at the next tgp_ivr_values and again
+ *     after every call that changes the handle's factor (tgp_set_hyper + tgp_set_data, tgp_append_data, tgp_clone_from INTO this
+ *     handle).  tgp_clone_from does NOT copy the setting: the destination keeps its own, or none.
+ *   tgp_ivr_values: Xq [G,q,d], 1 <= q <= TGP_IVR_MAX_Q else TGP_ERR_SHAPE; out / reduction [G], either may be NULL, not both
+ *     (TGP_ERR_ARG).  reduction[g] = (1/P) sum_z w_z sum_i a_iz^2 >= 0, a_.z = L_g^-1 c_.z, L_g = chol(Sigma_xx,g + s^2 I);
+ *     out[g] = reduction[g] - c0 = the reference's -reduce_mean(variance * weights) (active_learning.py:409-415).  The reduction is
+ *     10^2 .. 10^4 times smaller than c0: it carries the digits out has lost.  Chunks of 2048 / q groups: the small-product
+ *     posterior of the chunk, one more product (W K*)^T C_Z, the tail kernel; nothing of size G q P leaves the device.  A group's
+ *     bits may depend on how many groups share its chunk (the products split k by their tile count, as tgp_predict_joint's
+ *     small path does); identical calls return identical bits.  TGP_ERR_STATE without data or without integration points;
+ *     TGP_ERR_NOT_PD names the group (0-based, of the call) whose factorisation broke down.
+ *   tgp_ivr_last_ms: device time of the last tgp_ivr_values, summed over its chunks: posterior, cross product, tail.
+ *   tgp_ivr_moments: the tail alone on given moments, no model needed (the counterpart of tgp_qei_moments): cov [G,q,q] (lower
+ *     triangle and diagonal read), cross [G,q,P], weights [P] or NULL, noise >= 0 added to cov's diagonal -> reduction [G].
+ *     Chunks of 2^28 / (8 q P) groups.  The weights are taken as given. */
+#define TGP_IVR_MAX_Q 16
+#define TGP_IVR_MAX_P 16384
+int tgp_set_integration_points(tgp_handle h, const double* Z, int64_t P, const double* weights, int where);
+int tgp_ivr_values(tgp_handle h, const double* Xq, int64_t G, int q, double* out, double* reduction, int where);
+int tgp_ivr_last_ms(tgp_handle h, double* posterior_ms, double* cross_ms, double* tail_ms);
+int tgp_ivr_moments(tgp_handle h, const double* cov, const double* cross, const double* weights, int64_t G, int q, int64_t P,
+                    double noise, double* reduction, int where);
+
 /* == value and gradient of a BATCH acquisition function at the handful of q-batches an L-BFGS-B iteration holds: the reference
  * optimises BatchMonteCarloExpectedImprovement through batchify_joint(generate_continuous_optimizer) (acquisition/optimizer.py:
  * 897-934, 344-560) with tfp.math.value_and_gradient (optimizer.py:628-629), i.e. autodiff THROUGH predict_joint

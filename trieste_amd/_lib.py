@@ -78,6 +78,10 @@ SIGNATURES = {
     "tgp_qei_moments": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, C.c_int]),
     "tgp_qei_moments_grad": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp,
                                        C.c_int]),
+    "tgp_set_integration_points": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int]),
+    "tgp_ivr_values": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int]),
+    "tgp_ivr_last_ms": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "tgp_ivr_moments": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_double, _vp, C.c_int]),
     "tgp_traj_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_create_rff": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_get_theta": (C.c_int, [_vp, _vp]),
@@ -170,6 +174,7 @@ MAX_D = 1024      # input dimensions tgp_create accepts (include/tgp.h)
 NARROW_MAX_D = 32  # above it: float64 sweeps only (no int8 rungs), no trajectories
 EHVI_MAX_P, EHVI_MAX_BOUNDS, EHVI_MAX_CELLS = 4, 512, 1 << 21  # limits of the tgp_ehvi_* calls (include/tgp.h)
 QEHVI_MAX_Q = 8  # points per batch of the tgp_qehvi_* calls (TGP_QEHVI_MAX_Q)
+IVR_MAX_Q, IVR_MAX_P = 16, 16384  # points per batch / integration points of the tgp_ivr_* calls (TGP_IVR_MAX_Q, TGP_IVR_MAX_P)
 
 
 def check(lib, handle, rc, group=False):

@@ -3,6 +3,7 @@ survey marks out of scope that were built in round 1 (trust regions, asynchronou
 search and its Gumbel min-value sampler, the small builders NegativePredictiveMean / ProbabilityOfFeasibility / MakePositive /
 MultipleOptimismNegativeLowerConfidenceBound / PredictiveVariance / ExpectedConstrainedImprovement) are in
 :mod:`trieste_amd.extras`; this package exports SURVEY section 8 rows only."""
+from .active_learning import IntegratedVarianceReduction, integrated_variance_reduction
 from .continuous_thompson_sampling import (GreedyContinuousThompsonSampling, ParallelContinuousThompsonSampling,
                                            negate_trajectory_function)
 from .function import (AugmentedExpectedImprovement, BatchExpectedImprovement, BatchMonteCarloExpectedImprovement,

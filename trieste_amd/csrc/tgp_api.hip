@@ -1158,13 +1158,15 @@ int tgp_destroy(tgp_handle h) {
   for (DevBuf* b : {&h->d_xc, &h->d_xn, &h->d_xc32, &h->d_pre, &h->d_ls, &h->d_X, &h->d_Y, &h->d_Xs, &h->d_A, &h->d_L, &h->d_W, &h->d_alpha,
                     &h->d_err, &h->d_tmp1, &h->d_tmp2, &h->d_info, &h->d_pen, &h->d_ent, &h->d_ehvi, &h->s_ehvi, &h->d_repv, &h->d_wq, &h->d_rs, &h->d_xsa, &h->s_ent, &h->s_in, &h->s_in2, &h->s_out1,
                     &h->s_out2, &h->s_out3, &h->s_blkv, &h->s_blki, &h->s_small, &h->s_kcache, &h->s_aslab, &h->s_grad, &h->s_ks, &h->s_part, &h->s_xqw, &h->s_rep, &h->s_prune,
-                    &h->s_rep_stats, &h->d_dag_flags, &h->d_dag_trace})
+                    &h->s_rep_stats, &h->d_dag_flags, &h->d_dag_trace, &h->d_ivr_z, &h->d_ivr_w, &h->d_ivr_zt, &h->d_ivr_cz, &h->d_ivr_c0})
     b->release();
 
   if (h->rep_host) (void)hipHostFree(h->rep_host);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_order) (void)hipEventDestroy(h->ev_order);
+  for (hipEvent_t e : h->ev_ivr)
+    if (e) (void)hipEventDestroy(e);
   delete h;
   (void)hipGetLastError();  // do not leave a cleanup error behind for the thread's next launch check
   return TGP_OK;
@@ -2792,6 +2794,191 @@ int tgp_qei_moments_grad(tgp_handle h, const double* mean, const double* cov, in
     return bracketed(h, [&] {
       launch_qei_grad_tail(h->stream, m[M_MEAN].dev, m[M_COV].dev, gc, q, deps, S, eta, jitter, m[M_VAL].dev, m[M_GMEAN].dev,
                            m[M_GCOV].dev, h->d_info.as<int>());
+    });
+  });
+}
+
+// ---- integrated variance reduction (tgp_kernels_ivr.hip) ---------------------------------------------------------------------------
+constexpr const char* IVR_NOT_PD = "IVR: cov + noise*I of group %lld is not positive definite";
+
+int tgp_set_integration_points(tgp_handle h, const double* Z, int64_t P, const double* weights, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (P == 0) {
+    h->ivr_P = 0;
+    h->ivr_version = 0;
+    return TGP_OK;
+  }
+  if (P < 1 || P > IVR_MAX_P)
+    return fail(h, TGP_ERR_SHAPE, "number of integration points must be in 1..%lld, got %lld", (long long)IVR_MAX_P, (long long)P);
+  if (!Z) return fail(h, TGP_ERR_ARG, "Z is NULL");
+  if (int rc = set_device(h)) return rc;
+  h->ivr_P = 0;
+  h->ivr_version = 0;
+  std::vector<double> w((size_t)P, 1.0);
+  if (weights) {
+    if (where == TGP_DEVICE) {
+      HIPCHK(h, hipMemcpyAsync(w.data(), weights, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+      std::copy(weights, weights + P, w.begin());
+    }
+    for (int64_t z = 0; z < P; ++z)
+      if (!(w[(size_t)z] >= 0.0) || !std::isfinite(w[(size_t)z]))
+        return fail(h, TGP_ERR_ARG, "integration weights must be finite and >= 0 (weight %lld is %g)", (long long)z, w[(size_t)z]);
+  }
+  HIPCHK(h, h->d_ivr_z.reserve((size_t)P * h->d * sizeof(double)));
+  HIPCHK(h, h->d_ivr_w.reserve((size_t)P * sizeof(double)));
+  HIPCHK(h, hipMemcpyAsync(h->d_ivr_z.p, Z, (size_t)P * h->d * sizeof(double),
+                           where == TGP_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_ivr_w.p, w.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays (and w) may be released on return
+  h->ivr_P = P;
+  return TGP_OK;
+}
+
+// What tgp_ivr_values needs of (model, Z), once per factorisation: Z / l transposed, C_Z = W k(X, Z) [Npad][Ppad], and
+// c0 = (1/P) sum_z w_z var_old(z).  Z goes through tgp_predict's small-product path in pieces of SMALL_PREDICT_M points (K*^T,
+// W K*, the small-predict tail): var_old is tgp_predict's clipped variance, and each piece's W K* is copied into its columns of C_Z.
+static int ivr_prepare(tgp_handle h) {
+  if (h->ivr_version == h->data_version) return TGP_OK;
+  const int64_t P = h->ivr_P, Ppad = ((P + 63) / 64) * 64, Npad = h->Npad, piece = 2048;
+  const ModelDev m = model_dev(h);
+  HIPCHK(h, h->d_ivr_zt.reserve((size_t)h->d * Ppad * sizeof(double)));
+  HIPCHK(h, h->d_ivr_cz.reserve((size_t)Npad * Ppad * sizeof(double)));
+  HIPCHK(h, h->d_ivr_c0.reserve((size_t)(Ppad + 1) * sizeof(double)));
+  double* const var = h->d_ivr_c0.as<double>();
+  launch_ivr_scale_z(h->stream, h->d_ivr_z.as<double>(), m.ls, P, h->d, Ppad, h->d_ivr_zt.as<double>());
+  const int64_t pp_max = std::min(Ppad, piece);
+  double *B, *C1, *part;
+  if (int rc = carve(h, h->s_grad, {{&B, (size_t)Npad * pp_max}, {&C1, (size_t)Npad * pp_max}, {&part, predict_small_scratch_doubles(pp_max)}}))
+    return rc;
+  for (int64_t z0 = 0; z0 < P; z0 += piece) {
+    const int64_t pc = std::min(piece, P - z0), pcp = ((pc + 63) / 64) * 64;
+    if (int rc = kstar_products(h, m, h->d_W.as<double>(), Npad, h->d_ivr_z.as<double>() + z0 * h->d, pc, pcp, B, C1)) return rc;
+    launch_predict_small_tail(h->stream, m, pc, pcp, B, C1, part, nullptr, var + z0);
+    HIPCHK(h, hipMemcpy2DAsync(h->d_ivr_cz.as<double>() + z0, (size_t)Ppad * sizeof(double), C1, (size_t)pcp * sizeof(double),
+                               (size_t)pcp * sizeof(double), (size_t)Npad, hipMemcpyDeviceToDevice, h->stream));
+  }
+  launch_ivr_c0(h->stream, h->d_ivr_w.as<double>(), var, P, var + Ppad);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipGetLastError());
+  h->ivr_version = h->data_version;
+  return TGP_OK;
+}
+
+int tgp_ivr_values(tgp_handle h, const double* Xq, int64_t G, int q, double* out, double* reduction, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (!h->have_data) return fail(h, TGP_ERR_STATE, "model has no data: call tgp_set_data first");
+  if (h->ivr_P == 0) return fail(h, TGP_ERR_STATE, "no integration points set: call tgp_set_integration_points first");
+  if (q < 1 || q > IVR_MAX_Q) return fail(h, TGP_ERR_SHAPE, "IVR: q must be in 1..%d, got %d", IVR_MAX_Q, q);
+  if (G < 0 || (G > 0 && !Xq)) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (!out && !reduction) return fail(h, TGP_ERR_ARG, "out and reduction are both NULL");
+  if (G == 0) return TGP_OK;
+  if (int rc = set_device(h)) return rc;
+  if (int rc = ivr_prepare(h)) return rc;
+  if (!h->ev_ivr[0]) {
+    HIPCHK(h, hipEventCreate(&h->ev_ivr[0]));
+    HIPCHK(h, hipEventCreate(&h->ev_ivr[1]));
+  }
+  const int64_t Pz = h->ivr_P, Pzp = ((Pz + 63) / 64) * 64, Npad = h->Npad, d = h->d;
+  const ModelDev m = model_dev(h);
+  h->ivr_ms[0] = h->ivr_ms[1] = h->ivr_ms[2] = 0.0;
+  bool pending = false;   // a chunk's events wait to be read (its stream has drained when the next chunk, or the end, comes)
+  auto fold = [&] {
+    float a = 0.f, b = 0.f, c = 0.f;
+    if (pending && hipEventElapsedTime(&a, h->ev0, h->ev_ivr[0]) == hipSuccess &&
+        hipEventElapsedTime(&b, h->ev_ivr[0], h->ev_ivr[1]) == hipSuccess && hipEventElapsedTime(&c, h->ev_ivr[1], h->ev1) == hipSuccess) {
+      h->ivr_ms[0] += a;
+      h->ivr_ms[1] += b;
+      h->ivr_ms[2] += c;
+    }
+    pending = false;
+  };
+  // chunks of JOINT_SMALL_P points: the posterior of the chunk (K*^T, W K*, the Gram product, mean and the q x q covariances),
+  // the cross product S = (W K*)^T C_Z on the transpose the Gram product left in T, the tail.  Nothing of size G q P leaves the device.
+  const int rc = for_group_chunks(h, G, JOINT_SMALL_P / q, true, IVR_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    fold();
+    const int64_t Pc = gc * q, Pcp = ((Pc + 63) / 64) * 64;
+    const double* dXq;
+    double *dout, *dred;
+    if (int rb = stage_in(h, h->s_in, Xq + g0 * q * d, (size_t)Pc * d, where, &dXq)) return rb;
+    if (int rb = stage_out_prepare(h, h->s_out1, out ? out + g0 : nullptr, (size_t)gc, where, &dout)) return rb;
+    if (int rb = stage_out_prepare(h, h->s_out2, reduction ? reduction + g0 : nullptr, (size_t)gc, where, &dred)) return rb;
+    JointScratch w{};
+    double* Sxz;
+    const size_t np = (size_t)Npad * Pcp;
+    if (int rb = carve(h, h->s_grad, {{&w.B, np}, {&w.C1, np}, {&w.T, np}, {&w.S, (size_t)Pcp * Pcp}, {&Sxz, (size_t)Pcp * Pzp},
+                                      {&w.part, predict_small_scratch_doubles(Pcp)}, {&w.mean, (size_t)Pc}, {&w.cov, (size_t)Pc * q}}))
+      return rb;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    if (int rb = joint_forward(h, w, dXq, Pc, Pcp, q, w.mean, w.cov)) return rb;
+    HIPCHK(h, hipEventRecord(h->ev_ivr[0], h->stream));
+    if (int rb = gemm_tall(h, false, (int)Pcp, (int)Pzp, (int)Npad, 1.0, w.T, Npad, h->d_ivr_cz.as<double>(), Pzp, 0.0, Sxz, Pzp, 0))
+      return rb;
+    HIPCHK(h, hipEventRecord(h->ev_ivr[1], h->stream));
+    IvrTailArgs a{};
+    a.cov = w.cov;
+    a.noise = h->noise;
+    a.q = q;
+    a.d = (int)d;
+    a.kind = h->kind;
+    a.P = Pz;
+    a.ldz = Pzp;
+    a.weights = h->d_ivr_w.as<double>();
+    a.Xq = dXq;
+    a.ls = m.ls;
+    a.Zt = h->d_ivr_zt.as<double>();
+    a.S = Sxz;
+    a.variance = h->variance;
+    a.c0 = h->d_ivr_c0.as<double>() + Pzp;
+    a.reduction = dred;
+    a.out = dout;
+    a.info = h->d_info.as<int>();
+    launch_ivr_tail(h->stream, a, gc);
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    pending = true;
+    if (int rb = stage_out_finish(h, dout, out ? out + g0 : nullptr, (size_t)gc, where)) return rb;
+    return stage_out_finish(h, dred, reduction ? reduction + g0 : nullptr, (size_t)gc, where);
+  });
+  fold();
+  return rc;
+}
+
+int tgp_ivr_last_ms(tgp_handle h, double* posterior_ms, double* cross_ms, double* tail_ms) {
+  if (!h) return TGP_ERR_ARG;
+  if (posterior_ms) *posterior_ms = h->ivr_ms[0];
+  if (cross_ms) *cross_ms = h->ivr_ms[1];
+  if (tail_ms) *tail_ms = h->ivr_ms[2];
+  return TGP_OK;
+}
+
+int tgp_ivr_moments(tgp_handle h, const double* cov, const double* cross, const double* weights, int64_t G, int q, int64_t P,
+                    double noise, double* reduction, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (q < 1 || q > IVR_MAX_Q) return fail(h, TGP_ERR_SHAPE, "IVR: q must be in 1..%d, got %d", IVR_MAX_Q, q);
+  if (P < 1 || P > IVR_MAX_P)
+    return fail(h, TGP_ERR_SHAPE, "number of integration points must be in 1..%lld, got %lld", (long long)IVR_MAX_P, (long long)P);
+  if (G < 0 || !(noise >= 0.0)) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (G == 0) return TGP_OK;
+  if (!cov || !cross || !reduction) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  const double* dw = nullptr;
+  if (weights)
+    if (int rc = stage_in(h, h->s_in2, weights, (size_t)P, where, &dw)) return rc;
+  // the cross-covariances take the mean's place among the staged arrays ([G][q P]); a chunk's within 256 MiB
+  MomentArrays m = moment_arrays(h, 1, (int64_t)q * P, (int64_t)q * q, cross, cov, reduction);
+  return moments_chunks(h, G, groups_within(1ull << 28, (int64_t)q * P), IVR_NOT_PD, where, m, [&](int64_t gc, int64_t) {
+    return bracketed(h, [&] {
+      IvrTailArgs a{};
+      a.cov = m[M_COV].dev;
+      a.noise = noise;
+      a.q = q;
+      a.P = P;
+      a.weights = dw;
+      a.cross = m[M_MEAN].dev;
+      a.reduction = m[M_VAL].dev;
+      a.info = h->d_info.as<int>();
+      launch_ivr_tail(h->stream, a, gc);
     });
   });
 }

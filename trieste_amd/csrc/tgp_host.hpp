@@ -144,6 +144,15 @@ struct tgp_handle_s {
   DevBuf s_ehvi;   // tgp_ehvi_values / tgp_ehvi_argmax: the stack's moments, mean [P][M] then var [P][M] (16 P M bytes);
                    // tgp_ehvi_value_grad: those, their adjoints [P][M] each and the members' gradients [P][M][d]
   double ehvi_sweep_ms = 0.0, ehvi_tail_ms = 0.0;   // tgp_ehvi_last_ms
+  // integrated variance reduction (tgp_set_integration_points): the caller's points and weights, and what is derived from
+  // them AND the model, rebuilt lazily when ivr_version != data_version (tgp_api.hip ivr_prepare)
+  int64_t ivr_P = 0;
+  uint64_t ivr_version = 0;   // the factorisation the derived arrays were built from (0: none)
+  DevBuf d_ivr_z, d_ivr_w;    // Z [P][d], weights [P]
+  DevBuf d_ivr_zt, d_ivr_cz;  // Z / l transposed [d][Ppad];  C_Z = W k(X, Z) [Npad][Ppad]
+  DevBuf d_ivr_c0;            // var_old [Ppad], then c0 = (1/P) sum_z w_z var_old(z)
+  hipEvent_t ev_ivr[2] = {nullptr, nullptr};   // between ev0 and ev1: behind the posterior, behind the cross product
+  double ivr_ms[3] = {0.0, 0.0, 0.0};          // tgp_ivr_last_ms: posterior, cross product, tail of the last tgp_ivr_values
   tgp_handle rep_twin = nullptr;  // not owned: this model conditioned additionally on the pending points
   double rep_weight = 0.0;
   // when the twin is literally this model's data + m <= 16 appended rows (same hyper-parameters), its variance is

@@ -347,6 +347,30 @@ size_t qehvi_grad_lds_bytes(int P, int q, int S);
 void launch_qehvi_grad_tail(hipStream_t s, int P, int V, const double* bounds, const uint32_t* cells, int K, const double* mean,
                             const double* cov, int64_t G, int64_t gstride, int q, const double* eps, int S, double jitter,
                             int zero_clipped, double* val, double* gmean, double* gcov, int* info);
+// integrated variance reduction (tgp_kernels_ivr.hip): 1 <= q <= IVR_MAX_Q points per group, 1 <= P <= IVR_MAX_P integration points.
+// The cap: C_Z = W k(X, Z) [Npad][Ppad] is 512 MiB at N = 4096, a 2048-point chunk of the cross product S [2048][Ppad] 256 MiB.
+constexpr int IVR_MAX_Q = 16;
+constexpr int64_t IVR_MAX_P = 16384;
+struct IvrTailArgs {
+  const double* cov;       // [G][q][q] (lower triangle and diagonal read)
+  double noise;            // added to the diagonal
+  int q, d, kind;
+  int64_t P, ldz;          // integration points; row stride of S and Zt (P padded to 64)
+  const double* weights;   // [P] or null (all ones)
+  const double* cross;     // given moments: [G][q][P]; null: the cross-covariance is formed from the six below
+  const double* Xq;        // [G q][d]
+  const double* ls;        // [d]
+  const double* Zt;        // [d][ldz] = Z / l transposed
+  const double* S;         // [>= G q][ldz] = (W k(X, x))^T (W k(X, Z))
+  double variance;
+  const double* c0;        // one double, or null (0)
+  double *reduction, *out; // [G] each, either may be null: out = reduction - c0
+  int* info;
+};
+size_t ivr_tail_lds_bytes(int q, int d, bool given);
+void launch_ivr_tail(hipStream_t s, const IvrTailArgs& a, int64_t G);
+void launch_ivr_scale_z(hipStream_t s, const double* Z, const double* ls, int64_t P, int d, int64_t ldz, double* Zt);
+void launch_ivr_c0(hipStream_t s, const double* w, const double* var, int64_t P, double* c0);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

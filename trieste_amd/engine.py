@@ -832,6 +832,78 @@ def batch_ei_moments_grad(engine, mean, cov, w1, w2, eta: float):
     return outs
 
 
+IVR_MAX_Q, IVR_MAX_P = _lib.IVR_MAX_Q, _lib.IVR_MAX_P
+
+
+def set_integration_points(engine, Z, weights=None) -> None:
+    """The integration set of :func:`ivr_values`: Z [P, d] (1 <= P <= ``IVR_MAX_P``), weights [P] finite and >= 0 or None
+    (all ones), both numpy or both CUDA tensors; None or an empty Z clears the setting (tgp_set_integration_points).  Engine
+    state: the engine copies both, builds what depends on the model at the next ``ivr_values`` and rebuilds it whenever its
+    data or hyper-parameters change.  A clone does not inherit the setting.  Clears the engine's ``_ivr_owner`` mark."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "set_integration_points"):
+        return engine.set_integration_points(Z, weights)
+    engine._ivr_owner = None
+    if Z is None or int(np.prod(tuple(Z.shape) if hasattr(Z, "shape") else np.shape(Z))) == 0:
+        engine._chk(engine._lib.tgp_set_integration_points(engine._h, None, 0, None, _lib.HOST))
+        return
+    z = _Arg(Z)
+    if len(z.shape) != 2 or z.shape[1] != engine.d:
+        raise ValueError(f"integration points must be [P, {engine.d}], got {z.shape}")
+    P, pw = z.shape[0], None
+    if weights is not None:
+        w = _Arg(weights)
+        if int(np.prod(w.shape)) != P:
+            raise ValueError(f"weights must hold P={P} values, got shape {w.shape}")
+        if w.where != z.where:
+            raise ValueError("Z and weights must live in the same place (both host or both device)")
+        pw = w.ptr
+    engine._chk(engine._lib.tgp_set_integration_points(engine._h, z.ptr, P, pw, z.where))
+
+
+def ivr_values(engine, Xq, with_reduction: bool = False):
+    """Xq [..., q, d] (1 <= q <= ``IVR_MAX_Q``) -> [...]: the integrated variance reduction criterion of every q-batch over
+    the engine's integration points, the reference's ``-reduce_mean(conditional variance * weights)`` (tgp_ivr_values);
+    ``with_reduction=True`` -> (value, reduction), reduction >= 0 the query-dependent part, value = reduction - c0.  The
+    reduction is orders of magnitude smaller than the constant c0, so it keeps the digits the value has lost."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "ivr_values"):
+        return engine.ivr_values(Xq, with_reduction)
+    a, lead, q, G = _batch_points(engine.d, Xq)
+    if not 1 <= q <= IVR_MAX_Q:
+        raise ValueError(f"the integrated variance reduction takes 1 <= q <= {IVR_MAX_Q} points per batch, got {q}")
+    out, po = GPEngine._out(a, lead)
+    red, pr = GPEngine._out(a, lead) if with_reduction else (None, None)
+    engine._chk(engine._lib.tgp_ivr_values(engine._h, a.ptr, G, q, po, pr, a.where))
+    return (out, red) if with_reduction else out
+
+
+def ivr_last_ms(engine):
+    """Device time of the last :func:`ivr_values` -> (posterior, cross product, tail) in ms, summed over its chunks."""
+    p, c, t = C.c_double(), C.c_double(), C.c_double()
+    engine._chk(engine._lib.tgp_ivr_last_ms(engine._h, C.byref(p), C.byref(c), C.byref(t)))
+    return p.value, c.value, t.value
+
+
+def ivr_moments(engine, cov, cross, weights=None, noise: float = 0.0):
+    """The IVR tail on caller-supplied moments: cov [G, q, q] (``predict_joint``'s), cross [G, q, P] = cov(x_i, z), weights [P]
+    or None, ``noise`` added to cov's diagonal -> reduction [G] = (1/P) sum_z w_z |chol(cov + noise I)^-1 cross_.z|^2
+    (tgp_ivr_moments).  Needs no data on the engine."""
+    c, x = _Arg(cov), _Arg(cross)
+    if len(c.shape) != 3 or c.shape[1] != c.shape[2] or len(x.shape) != 3 or x.shape[:2] != c.shape[:2]:
+        raise ValueError(f"cov must be [G, q, q] and cross [G, q, P], got {c.shape} and {x.shape}")
+    G, q, P = x.shape
+    if not 1 <= q <= IVR_MAX_Q:
+        raise ValueError(f"the integrated variance reduction takes 1 <= q <= {IVR_MAX_Q} points per batch, got {q}")
+    w = None if weights is None else _Arg(weights)
+    if w is not None and int(np.prod(w.shape)) != P:
+        raise ValueError(f"weights must hold P={P} values, got shape {w.shape}")
+    if c.where != x.where or (w is not None and w.where != c.where):
+        raise ValueError("cov, cross and weights must live in the same place (all host or all device)")
+    out, po = GPEngine._out(c, (G,))
+    engine._chk(engine._lib.tgp_ivr_moments(engine._h, c.ptr, x.ptr, None if w is None else w.ptr, G, q, P, float(noise), po,
+                                            c.where))
+    return out
+
+
 def _qei_moment_args(mean, cov, eps):
     (m, c), e = _moment_pair(mean, cov, "G", same_place=False), _Arg(eps)
     G, q = m.shape
