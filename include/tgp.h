@@ -665,6 +665,11 @@ int tgp_get_prune_screened(tgp_handle h, int64_t* screened);
  * float64 mean pass did not run.  Never more than tgp_get_prune_screened; 0 under tgp_set_variant bits 12 and 14, at
  * Npad = 256 and when the most recent arg-max did not run the pruned kernel.  Synchronises the handle's stream. */
 int tgp_get_prune_prescreened(tgp_handle h, int64_t* prescreened);
+/* The few-blocks path of the handle's most recent arg-max: `prelisted`, the blocks the pre-screen left for
+ * the exact mean pass, and `tile_items`, the wave-tile work items its survivors were cut into -- 0 when the path was not
+ * taken (more blocks left than its cap, tgp_set_prune_split(0, ..), Npad = 256).  Both 0 under tgp_set_variant bit 15 and
+ * when that arg-max did not run the pruned kernel.  Synchronises the handle's stream. */
+int tgp_get_prune_tiles(tgp_handle h, int64_t* prelisted, int64_t* tile_items);
 /* The pre-screen's own quantities for M candidates Xq [M][d] (d <= 16): `mean32`, the posterior mean as the device forms it
  * in float32 kernel arithmetic, and `E`, the a-priori bound it holds for |mean32 - mean| per candidate.  A test and
  * measurement aid; `where` as in tgp_predict. */

@@ -7,7 +7,11 @@ without the seed and the mean screen, 8192 with blocks dealt statically (and 409
 tree without the pruned kernel the counters are left out (TGP_TREE=<checkout> imports the package of another checkout,
 e.g. the parent commit's, for the same-box comparison).  Each line carries the survivors of the list screen and the split
 work items (0: the survivors ran whole); --max-survivors 0 switches the split regime off, --max-groups caps the ranges per block.
-    python tools/bench_prune.py [--variant 2048] [--steps 10] [--warmup 3] [--workload headline|c2] [--max-survivors N] [--max-groups G]"""
+--variant 32768 runs without the few-blocks path; each line carries (blocks pre-listed, wave-tile items), items 0 when the path was
+not taken.  --few-sweep measures that path's cap: M = 128 P candidates for P = 1 .. 32 under bits 0 and 12 (the fused kernels, every
+block survives) and a split cap of P, the launch with bit 15 and the one without alternately in one process.
+    python tools/bench_prune.py [--variant 2048] [--steps 10] [--warmup 3] [--workload headline|c2] [--max-survivors N] [--max-groups G]
+                                [--few-sweep]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.environ.get("TGP_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -26,6 +30,7 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--workload", default="headline", choices=sorted(SHAPES))
 ap.add_argument("--max-survivors", type=int, default=-1, help="tgp_set_prune_split: -1 derived, 0 never split")
 ap.add_argument("--max-groups", type=int, default=0, help="tgp_set_prune_split: ranges per surviving block, 0 up to the row blocks")
+ap.add_argument("--few-sweep", action="store_true", help="the few-blocks path against bit 15 at M = 128 P, P = 1 .. 32")
 args = ap.parse_args()
 obj, d, kernel, N, M, noise = SHAPES[args.workload]
 X, Y = O.synthetic_problem(getattr(O, obj), d, N)
@@ -37,6 +42,24 @@ eng.use_torch_stream()
 eng.set_hyper(1.0, O.default_lengthscales(d), noise, float(Y.mean()))
 eng.set_data(X, Y)
 Xq = eng.sample_box(5678, 0, M, 0.0, 1.0)
+if args.few_sweep:
+    eta = eng.eta()
+    for P in (1, 2, 4, 8, 16, 32):
+        E.set_prune_split(eng, P, args.max_groups)
+        Xp = Xq[: 128 * P]
+        ms = {0: [], 32768: []}
+        for rep in range(args.warmup + args.steps):
+            for bit in (32768, 0):
+                eng.set_variant(1 | 4096 | bit)
+                best = eng.acq_argmax_pair("ei", eta, Xp, index_base=0)
+                torch.cuda.synchronize()
+                if rep >= args.warmup:
+                    ms[bit].append(eng.last_kernel_ms()[0])
+                if bit == 0:
+                    tiles = E.prune_tiles(eng)
+        print(json.dumps(dict(workload=args.workload, P=P, old_kernel_ms=float(np.median(ms[32768])), few_kernel_ms=float(np.median(ms[0])),
+                              ratio=float(np.median(ms[0]) / np.median(ms[32768])), prelisted_tile_items=tiles)), flush=True)
+    sys.exit(0)
 for label, eta in (("eta", eng.eta()), ("eta=-1e6", -1e6)):
     def step():
         v, i = all_gather_winners(eng, eng.acq_argmax_pair("ei", eta, Xq, index_base=0))
@@ -61,4 +84,6 @@ for label, eta in (("eta", eng.eta()), ("eta=-1e6", -1e6)):
         out["prescreened"] = E.prune_prescreened(eng)
     if hasattr(E, "prune_split"):
         out["survivors, items"] = E.prune_split(eng)
+    if hasattr(E, "prune_tiles"):
+        out["prelisted, tile items"] = E.prune_tiles(eng)
     print(json.dumps(out), flush=True)

@@ -121,6 +121,7 @@ SIGNATURES = {
     "tgp_get_prune_screened": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "tgp_get_prune_prescreened": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "tgp_prescreen_means": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int]),
+    "tgp_get_prune_tiles": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tgp_set_prune_split": (C.c_int, [_vp, C.c_int, C.c_int]),
     "tgp_get_prune_split": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tgp_set_variant": (C.c_int, [_vp, C.c_int]),

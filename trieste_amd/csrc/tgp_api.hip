@@ -187,7 +187,9 @@ void apply_penalization(tgp_handle h, double* dvals, const double* dXq, int64_t 
 constexpr int VARIANT_NO_SPLIT = 1, VARIANT_FORCE_SPLIT = 2, VARIANT_JOINT_V1 = 4, VARIANT_REG_STAGING = 8, VARIANT_NO_DAG = 16,
               VARIANT_DAG_SMALL = 32, VARIANT_NO_REPAIR_PRODUCT = 64, VARIANT_STATIC_BLOCKS = 128, VARIANT_DAG_WHOLE_TILES = 256,
               VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024, VARIANT_NO_PRUNE = 2048,
-              VARIANT_PRUNE_NO_SCREEN = 4096, VARIANT_PRUNE_STATIC_BLOCKS = 8192, VARIANT_PRUNE_NO_PRESCREEN = 16384;
+              VARIANT_PRUNE_NO_SCREEN = 4096, VARIANT_PRUNE_STATIC_BLOCKS = 8192, VARIANT_PRUNE_NO_PRESCREEN = 16384,
+              VARIANT_PRUNE_NO_FEW = 32768;
+//   VARIANT_PRUNE_NO_FEW (32768): without its few-blocks path (K* once per block, wave-tile work items) when phase 0 leaves a handful
 //   VARIANT_PRUNE_NO_PRESCREEN (16384): its mean pass over every block, without the float32 pre-screen in front (phase 0)
 //   VARIANT_PRUNE_NO_SCREEN (4096): the pruned EI arg-max without the seed and the mean screen (blocks are given up at checkpoints only)
 //   VARIANT_PRUNE_STATIC_BLOCKS (8192): its workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter
@@ -641,6 +643,9 @@ hipError_t launch_sweep_timed(tgp_handle h, SweepArgs a, bool joint) {
         pl.max_groups = h->prune_max_groups;
         static const bool mean4 = getenv("TGP_PRUNE_MEAN_WAVES4") != nullptr;  // A/B aid: phase 1 at four waves per SIMD
         pl.mean_waves = mean4 ? 4 : 8;
+        // the few-blocks path, chosen on the device when phase 0 leaves no more blocks than this: every one of them may
+        // survive (the dump area), each has a K* slab of its own, and PRUNE_FEW_MAX is where the measurement stopped
+        if (!(h->variant & VARIANT_PRUNE_NO_FEW)) pl.few_max = (int)std::min<int64_t>({PRUNE_FEW_MAX, pl.max_survivors, wg});
         words = PruneView::words(grid, pl.max_survivors, nb);
         // phase 0 reads what `update` left for THIS handle's model (a sweep over another handle's model does without)
         if (!(h->variant & (VARIANT_PRUNE_NO_SCREEN | VARIANT_PRUNE_NO_PRESCREEN)) && a.m.alpha == h->d_alpha.as<double>() &&
@@ -3404,6 +3409,15 @@ int tgp_get_prune_screened(tgp_handle h, int64_t* screened) {
   unsigned long long w[PRUNE_W_IB];
   if (int rc = read_prune_words(h, w)) return rc;
   if (screened) *screened = (int64_t)w[PRUNE_W_SCREENED];
+  return TGP_OK;
+}
+
+int tgp_get_prune_tiles(tgp_handle h, int64_t* prelisted, int64_t* tile_items) {
+  if (!h) return TGP_ERR_ARG;
+  unsigned long long w[PRUNE_W_IB];
+  if (int rc = read_prune_words(h, w)) return rc;
+  if (prelisted) *prelisted = (int64_t)w[PRUNE_W_PRELISTED];
+  if (tile_items) *tile_items = (int64_t)w[PRUNE_W_TILE_ITEMS];
   return TGP_OK;
 }
 

@@ -135,23 +135,28 @@ struct SweepArgs {
 //   PRUNE_W_IB ..     the range boundaries
 //   PRUNE_W_PREBEST   phase 0 (the float32 pre-screen): the bits of the largest lower seed eta - mean32 - E, rounded down; it is
 //                     never above what PRUNE_W_BEST ends at      PRUNE_W_PRESCREENED  blocks whose exact mean pass was skipped
+//   PRUNE_W_PRELISTED P, the blocks phase 0 left for the exact mean pass (prune_prelist_kernel)      PRUNE_W_FEW  non-zero: the
+//                     few-blocks path runs (1 <= P <= PruneLaunch::few_max)      PRUNE_W_TILE_ITEMS  its tile items (0: not taken)
 // and from word PRUNE_HDR_WORDS on the areas of PruneView.  Only the header is cleared per launch: everything else is
 // written before it is read.
 constexpr int PRUNE_W_BEST = 0, PRUNE_W_GIVEN_UP = 1, PRUNE_W_SKIPPED = 2, PRUNE_W_SCREENED = 3, PRUNE_W_DRAW = 4,
               PRUNE_W_SURVIVORS = 5, PRUNE_W_ITEMS = 6, PRUNE_W_GROUPS = 7, PRUNE_W_PREBEST = 8, PRUNE_W_PRESCREENED = 9,
-              PRUNE_W_IB = 16, PRUNE_MAX_GROUPS = 64,
+              PRUNE_W_PRELISTED = 10, PRUNE_W_FEW = 11, PRUNE_W_TILE_ITEMS = 12, PRUNE_W_IB = 16, PRUNE_MAX_GROUPS = 64,
               PRUNE_HDR_WORDS = 128;
 constexpr size_t PRUNE_DUMP_BLOCK = 32 * 1024;                   // doubles per (survivor, row block): 256 KiB
 constexpr size_t PRUNE_DUMP_MAX_BYTES = (size_t)1 << 30;         // the dump area never exceeds this, nor the launch's K* slabs
+constexpr int PRUNE_FEW_MAX = 32;                                // the few-blocks path: pre-listed blocks at the most
 struct PruneView {   // the areas behind the header of a launch over nblk candidate blocks
   unsigned long long* w;
   int64_t nblk;
   __host__ __device__ double* bounds() const { return (double*)(w + PRUNE_HDR_WORDS); }               // [nblk] blocks' bounds
   __host__ __device__ int64_t* list() const { return (int64_t*)(w + PRUNE_HDR_WORDS + nblk); }        // [nblk] survivors
   __host__ __device__ double* means() const { return (double*)(w + PRUNE_HDR_WORDS + 2 * nblk); }     // [nblk][128]
+  // the few-blocks path: pre-listed block p, whose K* is slab p of the launch
+  __host__ __device__ int64_t* prelist() const { return (int64_t*)(w + PRUNE_HDR_WORDS + (2 + SW_BN) * nblk); }   // [PRUNE_FEW_MAX]
   // the accumulator dump [survivor][row block of nb][32][1024], from a multiple of 32 words on
   static __host__ __device__ size_t dump_word(int64_t nblk) {
-    return ((size_t)PRUNE_HDR_WORDS + (size_t)nblk * (2 + SW_BN) + 31) / 32 * 32;
+    return ((size_t)PRUNE_HDR_WORDS + (size_t)nblk * (2 + SW_BN) + PRUNE_FEW_MAX + 31) / 32 * 32;
   }
   __host__ __device__ double* dump(int64_t survivor, int ib, int nb) const {
     return (double*)(w + dump_word(nblk)) + ((size_t)survivor * nb + ib) * PRUNE_DUMP_BLOCK;
@@ -193,6 +198,7 @@ struct PruneLaunch {
   const double* pre;   // [PRE_WORDS]: see PRE_*
   // the read-back of tgp_prescreen_means (null in the arg-max): per candidate the device's mean32 and its bound E
   double *m32_out, *e_out;
+  int few_max;         // the few-blocks path: the cap on pre-listed blocks (0: off), <= PRUNE_FEW_MAX, max_survivors and the slabs
 };
 // PruneLaunch::pre: |alpha|_1; the largest sqrt(SCALE) |Xs_k - Xs_0|_2 over the training rows; sqrt(SCALE) |Xs_0|_2;
 // sqrt(SCALE) itself

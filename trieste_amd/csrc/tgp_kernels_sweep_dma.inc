@@ -138,16 +138,16 @@ constexpr int PRUNE_NO_SCREEN = 1, PRUNE_STATIC_BLOCKS = 2;   // SweepArgs::prun
 // No workgroup waits for another.  Models of one row block keep the single launch.
 constexpr int GEN_MEAN = 1, GEN_SLAB = 2;
 
-// Every K* entry of k-steps [0, gmax) of a block, entry for entry the arithmetic of generate_B, k-steps in the order the
+// Every K* entry of k-steps [g0, gmax) of a block, entry for entry the arithmetic of generate_B, k-steps in the order the
 // sweep meets them -- folded into the mean (GEN_MEAN: nothing is stored), written to the slab (GEN_SLAB) or both.  One
 // function for the mean kernel and the sweep: the thread -> entry mapping and the order of the fma chain fix the mean's bits.
 template <int KIND, int DP, int WHAT>
 __device__ __forceinline__ void prune_generate(const SweepArgs& a, const double* xqs, int kcol, int krg, int gmax, double* kc,
-                                               double variance, double& macc) {
+                                               double variance, double& macc, int g0 = 0) {
   double xr[DP];
 #pragma unroll
   for (int c = 0; c < DP; ++c) xr[c] = xqs[c * DBN + kcol];
-  for (int g = 0; g < gmax; ++g) {
+  for (int g = g0; g < gmax; ++g) {
     const int64_t krow0 = (int64_t)g * DBK + 2 * krg;
     const cptr xs = as_const(a.m.Xs + krow0 * DP);
     const cptr al = as_const(a.m.alpha + krow0);
@@ -237,6 +237,7 @@ __global__ __launch_bounds__(1024, 4) void sweep_dma_kernel(const SweepArgs a) {
   if constexpr (PRUNE) {
     if (listed) {
       const unsigned long long* hdr = a.prune;
+      if (hdr[PRUNE_W_FEW]) return;   // the few-blocks path: the survivors are prune_tile_kernel's
       const int64_t* list = pv().list();
       nsurv = (int64_t)hdr[PRUNE_W_SURVIVORS];
       const int items = (int)hdr[PRUNE_W_ITEMS], groups = (int)hdr[PRUNE_W_GROUPS];
@@ -728,6 +729,33 @@ __global__ __launch_bounds__(1024, 8) void prune_prescreen_kernel(const SweepArg
 #endif
 
 #ifdef TGP_SWEEP_PRUNE_TU
+// The end of a block's mean pass, thread (kcol, krg) holding its fma chain `macc`: the 128 means stored, the seed posted, the
+// block's largest EI tail at the prior variance stored as its bound (a NaN bound as +inf: never screened).  mred [8][128] and
+// ubw [2] are LDS; the last barrier frees them, and whatever the caller read before the call, for the next block.
+__device__ __forceinline__ void prune_mean_epilogue(const SweepArgs& a, const PruneView& pv, int64_t blk, double macc, double* mred,
+                                                    double* ubw, bool screen) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  mred[(tid >> 7) * 128 + (tid & 127)] = macc;
+  __syncthreads();
+  if (tid < 128) {
+    const double pm = pv.means()[blk * DBN + tid] = mean_reduce(a, mred, tid);
+    const bool valid = blk * DBN + tid < a.M;
+    if (screen) post_seed(a, valid, pm, lane);
+    // the checkpoint's bound with an empty partial norm; columns past M have nothing to lose
+    double ub = -INFINITY;
+    if (valid) {
+      ub = acq_tail(ACQ_EI, a.acq_param, pm, fmax(a.m.variance, VAR_FLOOR), a.m.noise);
+      if (ub != ub) ub = INFINITY;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) ub = fmax(ub, __shfl_xor(ub, o, 64));
+    if (lane == 0) ubw[w] = ub;
+  }
+  __syncthreads();   // xqs and mred are rewritten by the next block
+  if (tid == 0) pv.bounds()[blk] = fmax(ubw[0], ubw[1]);
+}
+
 // Phase 1: the mean pass of every candidate block, blocks i, i + #WG, ... (a pass costs the same for every block).  Leaves
 // the block's 128 means, posts its seed as the fused kernel did and stores the largest EI tail at the prior variance over
 // its valid candidates (a NaN bound as +inf: never screened).  Gives nothing up.  No A / B stages, no accumulators, no
@@ -747,6 +775,7 @@ __global__ __launch_bounds__(1024, WAVES) void prune_mean_kernel(const SweepArgs
   const int64_t nblk = (a.M + DBN - 1) / DBN;
   const PruneView pv{a.prune, nblk};
   const bool screen = !(a.prune_flags & PRUNE_NO_SCREEN);
+  if (a.prune[PRUNE_W_FEW]) return;   // the few-blocks path: the means come from the slabs (prune_mean_slab_kernel)
   // phase 0 (zero when it did not run): written by the launch in front of this one, stable during this one
   const double prebest = __longlong_as_double((long long)a.prune[PRUNE_W_PREBEST]);
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -760,24 +789,7 @@ __global__ __launch_bounds__(1024, WAVES) void prune_mean_kernel(const SweepArgs
     __syncthreads();
     double macc = 0.0;
     prune_generate<KIND, DP, GEN_MEAN>(a, xqs, kcol, krg, nb * DKSTEPS, nullptr, variance, macc);
-    mred[krg * 128 + kcol] = macc;
-    __syncthreads();
-    if (tid < 128) {
-      const double pm = pv.means()[blk * DBN + tid] = mean_reduce(a, mred, tid);
-      const bool valid = blk * DBN + tid < a.M;
-      if (screen) post_seed(a, valid, pm, lane);
-      // the checkpoint's bound with an empty partial norm; columns past M have nothing to lose
-      double ub = -INFINITY;
-      if (valid) {
-        ub = acq_tail(ACQ_EI, a.acq_param, pm, fmax(variance, VAR_FLOOR), a.m.noise);
-        if (ub != ub) ub = INFINITY;
-      }
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) ub = fmax(ub, __shfl_xor(ub, o, 64));
-      if (lane == 0) ubw[w] = ub;
-    }
-    __syncthreads();   // xqs and mred are rewritten by the next block
-    if (tid == 0) pv.bounds()[blk] = fmax(ubw[0], ubw[1]);
+    prune_mean_epilogue(a, pv, blk, macc, mred, ubw, screen);
   }
 }
 
@@ -836,7 +848,201 @@ __global__ __launch_bounds__(1024) void prune_list_kernel(const SweepArgs a, con
     }
     a.prune[PRUNE_W_GROUPS] = (unsigned long long)groups;
     a.prune[PRUNE_W_ITEMS] = (unsigned long long)(S * groups);
+    // the few-blocks path (S <= P <= few_max <= max_survivors: the split regime above, so the fold runs and the dump fits)
+    if (a.prune[PRUNE_W_FEW]) a.prune[PRUNE_W_TILE_ITEMS] = (unsigned long long)(S * nb * 16);
   }
+}
+
+// ---- The few-blocks path (nb > 1; DESIGN.md 4.1) ----------------------------------------------------------------------------
+// When phase 0 leaves P <= few_max blocks, phases 1 and 2 concern a handful of 128-candidate blocks, and the kernels above
+// spend their time on one workgroup each: the mean pass of a block is one workgroup's 0.3 ms, every split item generates the
+// K* rows it meets again, and the longest item is one compute unit's matrix rate.  Here instead
+//   prune_prelist_kernel   lists the P blocks phase 1 would not skip and raises PRUNE_W_FEW;
+//   prune_kstar_kernel     generates the K* of pre-listed block p ONCE, into slab p, one k-step per work item;
+//   prune_mean_slab_kernel replays the mean's fma chain over the slab (same values, same order: same bits);
+//   prune_list_kernel      runs as ever;
+//   prune_tile_kernel      forms a survivor's row blocks one 64 x 32 wave tile per work item: every accumulator sees the fused
+//                          kernel's MFMAs in the fused order and goes to the dump word the split item writes;
+//   prune_fold_kernel      runs as ever.
+// prune_mean_kernel and the PRUNE sweep_dma_kernel return at once.  Every kernel has a fixed grid and reads P, S and the
+// flag from the header: no host synchronisation, no kernel waits for another.
+
+// One workgroup, behind phase 0: the blocks phase 1 would not skip (prune_mean_kernel's rule), compacted in block order.
+// Without phase 0 prebest is zero and every block is listed.
+__global__ __launch_bounds__(1024) void prune_prelist_kernel(const SweepArgs a, const PruneLaunch pl) {
+  __shared__ int wcnt[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  const PruneView pv{a.prune, nblk};
+  int64_t* prelist = pv.prelist();
+  const double prebest = __longlong_as_double((long long)a.prune[PRUNE_W_PREBEST]);
+  int64_t base = 0;
+  for (int64_t c0 = 0; c0 < nblk; c0 += 1024) {
+    const int64_t blk = c0 + tid;
+    const bool live = blk < nblk && !(prebest > PRUNE_MIN_BEST && pv.bounds()[blk] * PRUNE_MARGIN < prebest);
+    const unsigned long long vote = __ballot(live);
+    if (lane == 0) wcnt[w] = __popcll(vote);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int i = 0; i < 16; ++i) {
+      if (i < w) before += wcnt[i];
+      total += wcnt[i];
+    }
+    const int64_t pos = base + before + __popcll(vote & ((1ull << lane) - 1ull));
+    if (live && pos < (int64_t)pl.few_max) prelist[pos] = blk;
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    a.prune[PRUNE_W_PRELISTED] = (unsigned long long)base;
+    if (base >= 1 && base <= (int64_t)pl.few_max) {
+      a.prune[PRUNE_W_FEW] = 1ull;
+      a.prune[PRUNE_W_PRESCREENED] = (unsigned long long)(nblk - base);   // what prune_mean_kernel's skips would have counted
+    }
+  }
+}
+
+// Work item (pre-listed block p, k-step g): the 16 x 128 K* entries of the k-step into slab p -- one iteration of
+// prune_generate's loop, entry for entry what the sweep's own generation stores.
+template <int KIND, int DP>
+__global__ __launch_bounds__(1024) void prune_kstar_kernel(const SweepArgs a) {
+  __shared__ double xqs[DBN * DP];
+  if (!a.prune[PRUNE_W_FEW]) return;
+  const int tid = threadIdx.x;
+  const int kcol = tid & 127;
+  const int krg = __builtin_amdgcn_readfirstlane(tid >> 7);
+  const int64_t Npad = a.m.Npad;
+  const int ng = (int)(Npad / DBK);
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  const PruneView pv{a.prune, nblk};
+  const int64_t items = (int64_t)a.prune[PRUNE_W_PRELISTED] * ng;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int64_t p = item / ng;
+    const int g = (int)(item % ng);
+    const int64_t blk = pv.prelist()[p];
+    for (int e = tid; e < DBN * DP; e += 1024) scale_entry(xqs, a.Xq, a.M, a.m.d, a.m.ls, blk, e / DP, e % DP);
+    __syncthreads();
+    double macc = 0.0;
+    prune_generate<KIND, DP, GEN_SLAB>(a, xqs, kcol, krg, g + 1, a.kcache + (size_t)p * (size_t)Npad * DBN, a.m.variance, macc, g);
+    __syncthreads();   // xqs is rewritten by the next item
+  }
+}
+
+// One workgroup per pre-listed block: thread (kcol, krg) replays prune_generate's chain macc = fma(kv, alpha[row], macc) over
+// g = 0 .. and r = 0, 1 with kv read from the slab, then the mean pass's own epilogue.
+__global__ __launch_bounds__(1024) void prune_mean_slab_kernel(const SweepArgs a) {
+  __shared__ double mred[8 * DBN];
+  __shared__ double ubw[2];
+  if (!a.prune[PRUNE_W_FEW] || (unsigned long long)blockIdx.x >= a.prune[PRUNE_W_PRELISTED]) return;
+  const int tid = threadIdx.x;
+  const int kcol = tid & 127;
+  const int krg = __builtin_amdgcn_readfirstlane(tid >> 7);
+  const int64_t Npad = a.m.Npad;
+  const int ng = (int)(Npad / DBK);
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  const PruneView pv{a.prune, nblk};
+  const double* __restrict__ kc = a.kcache + (size_t)blockIdx.x * (size_t)Npad * DBN + (size_t)(2 * krg) * DBN + kcol;
+  double macc = 0.0;
+#pragma unroll 8
+  for (int g = 0; g < ng; ++g) {
+    const cptr al = as_const(a.m.alpha + (int64_t)g * DBK + 2 * krg);
+    const double k0 = kc[(size_t)g * DBK * DBN], k1 = kc[(size_t)g * DBK * DBN + DBN];
+    macc = fma(k0, al[0], macc);
+    macc = fma(k1, al[1], macc);
+  }
+  prune_mean_epilogue(a, pv, pv.prelist()[blockIdx.x], macc, mred, ubw, !(a.prune_flags & PRUNE_NO_SCREEN));
+}
+
+// Work item (survivor, row block ib, wave tile (wm, wn)), one wave: the 64 x 32 tile of C = W K* the fused kernel's wave
+// (wm, wn) holds at the end of row block ib.  Per accumulator one mfma_f64(av, bv, acc) per k4 round, k-steps in the order
+// (kb = 0 .. ib, ks = 0 .. 15) from zero -- the rows of step s = 16 kb + ks are 16 s .. 16 s + 15 -- and the fused kernel's
+// whole-quarter skip (kb == ib and 16 ks >= 64 wm + 64), which cuts the tail of the order: steps [0, 16 ib + 4 wm + 4).
+// The operands come straight from Wt and the survivor's slab, lane for lane what dma_kstep reads from LDS, four k-steps
+// of them in registers at a time (a wave has the SIMD's registers to itself).  What the compiled loop does with them: the
+// hardware counts 63 loads in flight and a step is 24, and the compiler waits ONCE per four steps, with vmcnt(24) at the
+// top of the body -- there steps s .. s + 2 have landed and only the loads of s + 3, just issued, are out.  The loads of
+// s + 4, s + 5, s + 6 go out behind the MFMAs of s, s + 1, s + 2, so the youngest has one step of MFMAs (32 x 64 cycles)
+// of lead before that wait, the others two and three.  Measured: SQ_WAIT_ANY is 9 % of the wave cycles at the headline
+// (profiles/r29_prune_tiles.txt).  Items are ordered longest row block first.
+constexpr int TILE_DEPTH = 4;
+__device__ __forceinline__ void tile_load(double (&av)[16], double (&bv)[8], const double* ap, const double* bp, int64_t Npad, int s) {
+  const double* a0 = ap + (int64_t)s * DBK * Npad;
+  const double* b0 = bp + (int64_t)s * DBK * DBN;
+#pragma unroll
+  for (int k4 = 0; k4 < 4; ++k4) {
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm) av[k4 * 4 + fm] = a0[(int64_t)k4 * 4 * Npad + fm * 16];
+#pragma unroll
+    for (int fn = 0; fn < 2; ++fn) bv[k4 * 2 + fn] = b0[k4 * 4 * DBN + fn * 16];
+  }
+}
+__device__ __forceinline__ void tile_step(v4d (&acc)[4][2], const double (&av)[16], const double (&bv)[8]) {
+#pragma unroll
+  for (int k4 = 0; k4 < 4; ++k4)
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn) acc[fm][fn] = mfma_f64(av[k4 * 4 + fm], bv[k4 * 2 + fn], acc[fm][fn]);
+}
+__global__ __launch_bounds__(64) void prune_tile_kernel(const SweepArgs a) {
+  if (!a.prune[PRUNE_W_FEW]) return;
+  const int64_t Npad = a.m.Npad;
+  const int nb = (int)(Npad / DBM);
+  const int64_t S = (int64_t)a.prune[PRUNE_W_SURVIVORS];
+  if ((int64_t)blockIdx.x >= S * nb * 16) return;
+  const int lane = threadIdx.x;
+  const int wt = (int)(blockIdx.x & 15u), wm = wt >> 2, wn = wt & 3;
+  const int64_t q = blockIdx.x >> 4;
+  const int srv = (int)(q % S), ib = nb - 1 - (int)(q / S);
+  const int64_t nblk = (a.M + DBN - 1) / DBN;
+  const PruneView pv{a.prune, nblk};
+  // the survivor's slab: its position in the pre-list (every survivor is pre-listed)
+  const int64_t blk = pv.list()[srv];
+  const int P = (int)a.prune[PRUNE_W_PRELISTED];
+  const unsigned long long hit = __ballot(lane < P && pv.prelist()[lane < P ? lane : 0] == blk);
+  const int p = __builtin_amdgcn_readfirstlane(hit ? __ffsll((long long)hit) - 1 : 0);
+  const double* ap = a.m.Wt + (int64_t)(lane >> 4) * Npad + (int64_t)ib * DBM + wm * 64 + (lane & 15);
+  const double* bp = a.kcache + (size_t)p * (size_t)Npad * DBN + (lane >> 4) * DBN + wn * 32 + (lane & 15);
+  const int steps = ib * DKSTEPS + wm * 4 + 4;
+  v4d acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
+  // (loads past the last step repeat it: in bounds, unused, and the loop body has no branch)
+  auto at = [&](int s) { return s < steps ? s : steps - 1; };
+  double av0[16], bv0[8], av1[16], bv1[8], av2[16], bv2[8], av3[16], bv3[8];
+  // The step count is a multiple of four: the loop body is four steps and one basic block.  The scheduling barriers keep
+  // every step's loads in front of the MFMAs they overlap (left alone, the compiler sinks them behind the MFMAs and waits
+  // for memory with nothing in flight).
+  tile_load(av0, bv0, ap, bp, Npad, 0);
+  tile_load(av1, bv1, ap, bp, Npad, 1);
+  tile_load(av2, bv2, ap, bp, Npad, 2);
+  for (int s = 0; s < steps; s += TILE_DEPTH) {
+    tile_load(av3, bv3, ap, bp, Npad, s + 3);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step(acc, av0, bv0);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_load(av0, bv0, ap, bp, Npad, at(s + 4));
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step(acc, av1, bv1);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_load(av1, bv1, ap, bp, Npad, at(s + 5));
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step(acc, av2, bv2);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_load(av2, bv2, ap, bp, Npad, at(s + 6));
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step(acc, av3, bv3);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  double* dp = pv.dump(srv, ib, nb) + wt * 64 + lane;
+#pragma unroll
+  for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dp[((fm * 2 + fn) * 4 + r) * 1024] = acc[fm][fn][r];
 }
 
 // Phase 3, one workgroup per split survivor: thread (wave, lane) replays fold_block over its dumped accumulators for
@@ -908,8 +1114,15 @@ hipError_t launch_sweep_dma_dp(hipStream_t s, const SweepArgs& a, int64_t grid) 
 // stream order, no host synchronisation; what depends on the number of survivors is decided on the device.
 hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const SweepArgs& a, int64_t grid, const PruneLaunch& pl) {
   if (a.m.Npad / DBM <= 1) return launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
+  const int nb = (int)(a.m.Npad / DBM), ng = nb * DKSTEPS;
   hipError_t e = with_dp<16>(a.m.dp, [&](auto DP) {
     if (pl.xc32) launch_prune_prescreen<TGP_SWEEP_KIND, DP()>(s, a, 2 * grid, pl);   // two workgroups per compute unit
+    if (pl.few_max > 0) {   // the few-blocks path: taken or not on the device
+      hipLaunchKernelGGL(prune_prelist_kernel, dim3(1), dim3(1024), 0, s, a, pl);
+      hipLaunchKernelGGL((prune_kstar_kernel<TGP_SWEEP_KIND, DP()>), dim3((unsigned)std::min<int64_t>((int64_t)pl.few_max * ng, 8 * grid)),
+                         dim3(1024), 0, s, a);
+      hipLaunchKernelGGL(prune_mean_slab_kernel, dim3((unsigned)pl.few_max), dim3(1024), 0, s, a);
+    }
     launch_prune_mean<TGP_SWEEP_KIND, DP()>(s, a, grid, pl.mean_waves);
     return hipSuccess;
   });
@@ -917,6 +1130,7 @@ hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const
   hipLaunchKernelGGL(prune_list_kernel, dim3(1), dim3(1024), 0, s, a, pl, (int)grid);
   e = launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
   if (e != hipSuccess) return e;
+  if (pl.few_max > 0) hipLaunchKernelGGL(prune_tile_kernel, dim3((unsigned)(pl.few_max * nb * 16)), dim3(64), 0, s, a);
   if (pl.max_survivors > 0) hipLaunchKernelGGL(prune_fold_kernel, dim3((unsigned)pl.max_survivors), dim3(1024), 0, s, a);
   return hipGetLastError();
 }

@@ -624,6 +624,14 @@ def prune_prescreened(eng: "GPEngine"):
     return s.value
 
 
+def prune_tiles(eng: "GPEngine"):
+    """(blocks pre-listed for the exact mean pass, wave-tile work items) of ``eng``'s most recent arg-max
+    (tgp_get_prune_tiles); items is 0 when the few-blocks path was not taken.  Synchronises the engine's stream."""
+    p, t = C.c_int64(), C.c_int64()
+    eng._chk(eng._lib.tgp_get_prune_tiles(eng._h, C.byref(p), C.byref(t)))
+    return p.value, t.value
+
+
 def prescreen_means(eng: "GPEngine", Xq):
     """(mean32, E) per candidate: the posterior mean as the pre-screen forms it on the device and the bound it holds for
     |mean32 - mean| (tgp_prescreen_means).  A test and measurement aid."""
