@@ -768,8 +768,11 @@ int tgp_get_auto_strata(tgp_handle h, int64_t* checked2, int64_t* violations2, d
  * arg-max sweeps every candidate block to the end instead of giving up blocks that cannot win (same winner, bit for bit), bit 12 =
  * the pruned EI arg-max without the seed and the mean screen (blocks are given up at row-block boundaries only), bit 13 = its
  * workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter, bit 14 =
- * its exact mean pass over every block, without the float32 pre-screen in front (bits 12 - 14: A/B runs and tests; the
- * same winner and the same counters, bit for bit, under every combination).  Bits 0-3, 7, 8: every
+ * its exact mean pass over every block, without the float32 pre-screen in front, bit 15 = without its few-blocks path (K* once
+ * per block, wave-tile work items) when the pre-screen leaves a handful, bit 16 (65536) = the float32 pre-screen, in the
+ * arg-max and in tgp_prescreen_means, with one candidate per thread in scalar float32 instead of two as a packed pair
+ * (bits 12 - 16: A/B runs and tests; the same winner and the same counters, bit for bit, under every combination; bit 16 also
+ * the same mean32 and E).  Bits 0-3, 7, 8: every
  * setting computes the same arithmetic on every candidate / matrix entry, bit for bit; bits 4 - 6, 9: the same values up to the
  * rounding of another summation order (bit 10 as well). */
 int tgp_set_variant(tgp_handle h, int variant);

@@ -7,6 +7,7 @@ without the seed and the mean screen, 8192 with blocks dealt statically (and 409
 tree without the pruned kernel the counters are left out (TGP_TREE=<checkout> imports the package of another checkout,
 e.g. the parent commit's, for the same-box comparison).  Each line carries the survivors of the list screen and the split
 work items (0: the survivors ran whole); --max-survivors 0 switches the split regime off, --max-groups caps the ranges per block.
+--variant 65536 runs the pre-screen with one candidate per thread (scalar float32) instead of the packed pairs.
 --variant 32768 runs without the few-blocks path; each line carries (blocks pre-listed, wave-tile items), items 0 when the path was
 not taken.  --few-sweep measures that path's cap: M = 128 P candidates for P = 1 .. 32 under bits 0 and 12 (the fused kernels, every
 block survives) and a split cap of P, the launch with bit 15 and the one without alternately in one process.

@@ -188,7 +188,8 @@ constexpr int VARIANT_NO_SPLIT = 1, VARIANT_FORCE_SPLIT = 2, VARIANT_JOINT_V1 = 
               VARIANT_DAG_SMALL = 32, VARIANT_NO_REPAIR_PRODUCT = 64, VARIANT_STATIC_BLOCKS = 128, VARIANT_DAG_WHOLE_TILES = 256,
               VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024, VARIANT_NO_PRUNE = 2048,
               VARIANT_PRUNE_NO_SCREEN = 4096, VARIANT_PRUNE_STATIC_BLOCKS = 8192, VARIANT_PRUNE_NO_PRESCREEN = 16384,
-              VARIANT_PRUNE_NO_FEW = 32768;
+              VARIANT_PRUNE_NO_FEW = 32768, VARIANT_PRESCREEN_SCALAR = 65536;
+//   VARIANT_PRESCREEN_SCALAR (65536): phase 0 with one candidate per thread in scalar float32 (before the packed pairs; same bits)
 //   VARIANT_PRUNE_NO_FEW (32768): without its few-blocks path (K* once per block, wave-tile work items) when phase 0 leaves a handful
 //   VARIANT_PRUNE_NO_PRESCREEN (16384): its mean pass over every block, without the float32 pre-screen in front (phase 0)
 //   VARIANT_PRUNE_NO_SCREEN (4096): the pruned EI arg-max without the seed and the mean screen (blocks are given up at checkpoints only)
@@ -657,7 +658,8 @@ hipError_t launch_sweep_timed(tgp_handle h, SweepArgs a, bool joint) {
       ea = h->s_prune.reserve(words * sizeof(unsigned long long));
       if (ea != hipSuccess) return ea;
       a.prune = h->s_prune.as<unsigned long long>();
-      a.prune_flags = ((h->variant & VARIANT_PRUNE_NO_SCREEN) ? 1 : 0) | ((h->variant & VARIANT_PRUNE_STATIC_BLOCKS) ? 2 : 0);
+      a.prune_flags = ((h->variant & VARIANT_PRUNE_NO_SCREEN) ? 1 : 0) | ((h->variant & VARIANT_PRUNE_STATIC_BLOCKS) ? 2 : 0) |
+                      ((h->variant & VARIANT_PRESCREEN_SCALAR) ? 4 : 0);
     }
     TimedLaunch timed(h);
     if (!prune) return by_kind(launch_sweep_dma_kinds, h->kind)(h->stream, a, wg);
@@ -3448,6 +3450,7 @@ int tgp_prescreen_means(tgp_handle h, const double* Xq, int64_t M, double* mean3
   a.M = M;
   a.acq_kind = TGP_ACQ_EI;
   a.acq_param = 0.0;
+  a.prune_flags = (h->variant & VARIANT_PRESCREEN_SCALAR) ? 4 : 0;
   const int64_t nblk = (M + SW_BN - 1) / SW_BN;
   h->prune_blocks = 0;   // the header words below are not an arg-max's
   HIPCHK(h, h->s_prune.reserve(PruneView::words(nblk, 0, 1) * sizeof(unsigned long long)));

@@ -125,6 +125,7 @@ __device__ __forceinline__ void dma_kstep(v4d (&acc)[4][2], uint32_t la, uint32_
 constexpr int D_PRUNE_LDS = 5 * DBN + 3;   // [4][128] checkpoint norms, [128] means, two vote words, the drawn block
 constexpr double PRUNE_MIN_BEST = 1e-280, PRUNE_MARGIN = 1.0 + 0x1p-14;
 constexpr int PRUNE_NO_SCREEN = 1, PRUNE_STATIC_BLOCKS = 2;   // SweepArgs::prune_flags (tgp_set_variant bits 12, 13)
+constexpr int PRUNE_PRE_SCALAR = 4;   // (bit 16) read by the host's launch alone: phase 0 with one candidate per thread
 // Models of more than one row block run the pruned arg-max in THREE PHASES on one stream (DESIGN.md 4.1):
 //   0 prune_prescreen_kernel: every block's mean in float32 with a bound that holds by construction; phase 1 skips what
 //     that dismisses (below; tgp_set_variant bit 14 runs without it);
@@ -607,18 +608,30 @@ struct PreShape {
 };
 constexpr double PRE_TAIL_INFLATE = 1.0 + 4e-5, PRE_MIN_BOUND = 1e-290;   // (below PRUNE_MIN_BEST: a floor skips nothing new)
 
-template <int KIND>
-__device__ __forceinline__ float prescreen_shape(float q) {   // q = SCALE r^2 >= 0 (difference form)
+// The packed form (CPT = 2): a thread holds two candidates, columns kcol and kcol + 64 of its block, as the halves of a
+// 2-vector, and the distance, the polynomial and the product run on v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32 -- per half
+// the IEEE operation of the scalar instruction, on the same operands in the same order, so mean32, E, ub32 and the prebest
+// word keep their bits while the distance costs half the issue slots.  max, sqrt and exp have no packed form: per half.
+typedef float float2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float pre_fma(float x, float y, float z) { return fmaf(x, y, z); }
+__device__ __forceinline__ float2v pre_fma(float2v x, float2v y, float2v z) { return __builtin_elementwise_fma(x, y, z); }
+template <typename F>
+__device__ __forceinline__ float pre_each(float x, F f) { return f(x); }
+template <typename F>
+__device__ __forceinline__ float2v pre_each(float2v x, F f) { return float2v{f(x.x), f(x.y)}; }
+
+template <int KIND, typename V>
+__device__ __forceinline__ V prescreen_shape(V q) {   // q = SCALE r^2 >= 0 (difference form)
   if constexpr (KIND == KIND_RBF) {
-    return __builtin_amdgcn_exp2f(-q);
+    return pre_each(q, [](float x) { return __builtin_amdgcn_exp2f(-x); });
   } else {
     constexpr float IL = (float)(1.0 / TrajShape<KIND>::L2E), IL2 = (float)(1.0 / (3.0 * TrajShape<KIND>::L2E * TrajShape<KIND>::L2E));
-    const float qc = fmaxf(q, (float)TrajShape<KIND>::FLOOR);
-    const float v = __builtin_amdgcn_sqrtf(qc);
-    const float e = __builtin_amdgcn_exp2f(-v);
+    const V qc = pre_each(q, [](float x) { return fmaxf(x, (float)TrajShape<KIND>::FLOOR); });
+    const V v = pre_each(qc, [](float x) { return __builtin_amdgcn_sqrtf(x); });
+    const V e = pre_each(v, [](float x) { return __builtin_amdgcn_exp2f(-x); });
     if constexpr (KIND == KIND_M12) return e;
-    else if constexpr (KIND == KIND_M32) return fmaf(IL, v, 1.0f) * e;
-    else return fmaf(IL2, qc, fmaf(IL, v, 1.0f)) * e;
+    else if constexpr (KIND == KIND_M32) return pre_fma((V)IL, v, (V)1.0f) * e;
+    else return pre_fma((V)IL2, qc, pre_fma((V)IL, v, (V)1.0f)) * e;
   }
 }
 
@@ -631,15 +644,27 @@ __device__ __forceinline__ double prescreen_bound(const SweepArgs& a, const doub
   return pre[PRE_ALPHA_L1] * a.m.variance * (c32 + c64 + 0x1p-60) + 0x1p-50 * (fabs(m32) + fabs(a.acq_param));
 }
 
-template <int KIND, int DP>
+// CPT candidates per thread.  CPT = 1 (tgp_set_variant bit 16): thread (kcol = tid & 127, krg = tid >> 7), one block per pass.
+// CPT = 2: the workgroup takes two consecutive blocks per pass, one per half of 512 threads; in a half, wave krg holds the
+// block's 128 columns two to a lane.  Either way a candidate's chain is row group krg's rows 32 g + 4 krg .. + 3, g ascending,
+// and its eight partial sums are added in the order krg = 0 .. 7.  The half without a block (odd block count) runs the pass on
+// candidate 0, reaches every barrier and writes nothing.  (At DP = 16 the packed form holds two rows' q at a time, not four:
+// 32 registers of coordinates leave no room for more under the 64 of eight waves per SIMD.)
+template <int KIND, int DP, int CPT>
 __global__ __launch_bounds__(1024, 8) void prune_prescreen_kernel(const SweepArgs a, const PruneLaunch pl) {
-  __shared__ float xqs[DP * DBN];     // [DP][128] centred, scaled candidate coordinates
-  __shared__ double mred[8 * DBN];    // [8][128]
-  __shared__ double ubw[2], sdw[2];
+  static_assert(CPT == 1 || CPT == 2, "one candidate per thread, or two as a packed pair");
+  using V = std::conditional_t<CPT == 1, float, float2v>;
+  constexpr int HT = 1024 / CPT;                       // threads per block of candidates
+  constexpr int RB = (CPT == 2 && DP > 8) ? 2 : 4;     // rows whose q are live at once
+  __shared__ float xqs[CPT * DP * DBN];     // per half [DP][128] centred, scaled candidate coordinates
+  __shared__ double mred[CPT * 8 * DBN];    // per half [8][128]
+  __shared__ double ubw[CPT * 2], sdw[CPT * 2];
   const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kcol = tid & 127;
-  const int krg = __builtin_amdgcn_readfirstlane(tid >> 7);   // row group: rows 32 g + 4 krg .. + 3
+  const int half = CPT == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid >> 9);
+  const int ht = CPT == 1 ? tid : (tid & 511);
+  const int w = __builtin_amdgcn_readfirstlane(ht >> 6);
+  const int kcol = ht & (DBN / CPT - 1);
+  const int krg = CPT == 1 ? __builtin_amdgcn_readfirstlane(ht >> 7) : w;   // row group: rows 32 g + 4 krg .. + 3
   const int d = a.m.d;
   const int ng = (int)(a.m.Npad / 32);
   const double variance = a.m.variance;
@@ -648,43 +673,61 @@ __global__ __launch_bounds__(1024, 8) void prune_prescreen_kernel(const SweepArg
   const double rs = pl.pre[PRE_RS];
   typedef const __attribute__((address_space(4))) float* cfptr;
   const cfptr xc32 = (cfptr)(const __attribute__((address_space(1))) float*)(pl.xc32);
-  for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    for (int e = tid; e < DBN * DP; e += 1024) {
+  float* const xq = xqs + half * (DP * DBN);
+  double* const mr = mred + half * (8 * DBN);
+  for (int64_t blk0 = (int64_t)CPT * blockIdx.x; blk0 < nblk; blk0 += (int64_t)CPT * gridDim.x) {
+    const int64_t blk = blk0 + half;
+    for (int e = ht; e < DBN * DP; e += HT) {
       const int j = e / DP, c = e % DP;
       const int64_t cand = blk * DBN + j;
       const int64_t src = cand < a.M ? cand : 0;
       // centred in float64 FIRST (Xs_0 is row 0 of Xs), then rounded
-      xqs[c * DBN + j] = (c < d) ? (float)(rs * (a.Xq[src * d + c] / as_const(a.m.ls)[c] - as_const(a.m.Xs)[c])) : 0.0f;
+      xq[c * DBN + j] = (c < d) ? (float)(rs * (a.Xq[src * d + c] / as_const(a.m.ls)[c] - as_const(a.m.Xs)[c])) : 0.0f;
     }
     __syncthreads();
-    float xr[DP];
+    V xr[DP];
 #pragma unroll
-    for (int c = 0; c < DP; ++c) xr[c] = xqs[c * DBN + kcol];
-    double macc = 0.0;
+    for (int c = 0; c < DP; ++c) {
+      if constexpr (CPT == 1) xr[c] = xq[c * DBN + kcol];
+      else xr[c] = float2v{xq[c * DBN + kcol], xq[c * DBN + kcol + 64]};
+    }
+    double macc[CPT] = {};
     for (int g = 0; g < ng; ++g) {
       const int64_t krow0 = (int64_t)g * 32 + 4 * krg;
       const cfptr xs = xc32 + krow0 * DP;
       const cptr al = as_const(a.m.alpha + krow0);
-      float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-      for (int c = 0; c < DP; ++c) {
+      for (int r0 = 0; r0 < 4; r0 += RB) {
+        V q[RB] = {};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float t0 = xr[c] - xs[r * DP + c];
-          q[r] = fmaf(t0, t0, q[r]);
+        for (int c = 0; c < DP; ++c) {
+#pragma unroll
+          for (int r = 0; r < RB; ++r) {
+            const V t0 = xr[c] - xs[(r0 + r) * DP + c];
+            q[r] = pre_fma(t0, t0, q[r]);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+          const V f = prescreen_shape<KIND>(q[r]);
+          if constexpr (CPT == 1) {
+            macc[0] = fma((double)f, al[r0 + r], macc[0]);
+          } else {
+            macc[0] = fma((double)f.x, al[r0 + r], macc[0]);
+            macc[1] = fma((double)f.y, al[r0 + r], macc[1]);
+          }
         }
       }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) macc = fma((double)prescreen_shape<KIND>(q[r]), al[r], macc);
     }
-    mred[krg * 128 + kcol] = macc;
+    mr[krg * 128 + kcol] = macc[0];
+    if constexpr (CPT == 2) mr[krg * 128 + kcol + 64] = macc[1];
     __syncthreads();
-    if (tid < 128) {
+    if (ht < 128) {
       double sum = 0.0;
 #pragma unroll
-      for (int g = 0; g < 8; ++g) sum += mred[g * 128 + tid];
+      for (int g = 0; g < 8; ++g) sum += mr[g * 128 + ht];
       const double m32 = fma(variance, sum, a.m.mean_const);
-      const int64_t cand = blk * DBN + tid;
+      const int64_t cand = blk * DBN + ht;
       const bool valid = cand < a.M;
       double ub = -INFINITY, seed = 0.0;   // columns past M have nothing to lose
       if (valid) {
@@ -712,15 +755,15 @@ __global__ __launch_bounds__(1024, 8) void prune_prescreen_kernel(const SweepArg
         seed = fmax(seed, __shfl_xor(seed, o, 64));
       }
       if (lane == 0) {
-        ubw[w] = ub;
-        sdw[w] = seed;
+        ubw[2 * half + w] = ub;
+        sdw[2 * half + w] = seed;
       }
     }
     __syncthreads();   // xqs and mred are rewritten by the next block
-    if (tid == 0) {
-      const double ub = fmax(ubw[0], ubw[1]);
+    if (ht == 0 && blk < nblk) {
+      const double ub = fmax(ubw[2 * half], ubw[2 * half + 1]);
       pv.bounds()[blk] = ub;
-      const double seed = fmax(sdw[0], sdw[1]);
+      const double seed = fmax(sdw[2 * half], sdw[2 * half + 1]);
       // (one candidate without a finite bound takes the block's lower seed with it)
       if (ub < INFINITY && seed > 0.0) atomicMax(a.prune + PRUNE_W_PREBEST, (unsigned long long)__double_as_longlong(seed));
     }
@@ -1084,7 +1127,8 @@ __global__ __launch_bounds__(1024) void prune_fold_kernel(const SweepArgs a) {
 
 template <int KIND, int DP>
 void launch_prune_prescreen(hipStream_t s, const SweepArgs& a, int64_t wg, const PruneLaunch& pl) {
-  hipLaunchKernelGGL((prune_prescreen_kernel<KIND, DP>), dim3((unsigned)wg), dim3(1024), 0, s, a, pl);
+  if (a.prune_flags & PRUNE_PRE_SCALAR) hipLaunchKernelGGL((prune_prescreen_kernel<KIND, DP, 1>), dim3((unsigned)wg), dim3(1024), 0, s, a, pl);
+  else hipLaunchKernelGGL((prune_prescreen_kernel<KIND, DP, 2>), dim3((unsigned)wg), dim3(1024), 0, s, a, pl);
 }
 template <int KIND, int DP>
 void launch_prune_mean(hipStream_t s, const SweepArgs& a, int64_t wg, int waves) {
