@@ -770,9 +770,11 @@ int tgp_get_auto_strata(tgp_handle h, int64_t* checked2, int64_t* violations2, d
  * workgroups take candidate blocks i, i + #WG, ... instead of drawing them from a counter, bit 14 =
  * its exact mean pass over every block, without the float32 pre-screen in front, bit 15 = without its few-blocks path (K* once
  * per block, wave-tile work items) when the pre-screen leaves a handful, bit 16 (65536) = the float32 pre-screen, in the
- * arg-max and in tgp_prescreen_means, with one candidate per thread in scalar float32 instead of two as a packed pair
- * (bits 12 - 16: A/B runs and tests; the same winner and the same counters, bit for bit, under every combination; bit 16 also
- * the same mean32 and E).  Bits 0-3, 7, 8: every
+ * arg-max and in tgp_prescreen_means, with one candidate per thread in scalar float32 instead of two as a packed pair,
+ * bit 18 (262144) = the few-blocks path's wave tiles as whole work items, never cut in halves or quarters while they leave
+ * SIMDs idle; bit 17 is not assigned
+ * (bits 12 - 16, 18: A/B runs and tests; the same winner and the same counters, bit for bit, under every combination; bit 16
+ * also the same mean32 and E).  Bits 0-3, 7, 8: every
  * setting computes the same arithmetic on every candidate / matrix entry, bit for bit; bits 4 - 6, 9: the same values up to the
  * rounding of another summation order (bit 10 as well). */
 int tgp_set_variant(tgp_handle h, int variant);

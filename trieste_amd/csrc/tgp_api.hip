@@ -188,7 +188,8 @@ constexpr int VARIANT_NO_SPLIT = 1, VARIANT_FORCE_SPLIT = 2, VARIANT_JOINT_V1 = 
               VARIANT_DAG_SMALL = 32, VARIANT_NO_REPAIR_PRODUCT = 64, VARIANT_STATIC_BLOCKS = 128, VARIANT_DAG_WHOLE_TILES = 256,
               VARIANT_DAG_ONE_CHAIN = 512, VARIANT_SWEEP_SMALL_PREDICT = 1024, VARIANT_NO_PRUNE = 2048,
               VARIANT_PRUNE_NO_SCREEN = 4096, VARIANT_PRUNE_STATIC_BLOCKS = 8192, VARIANT_PRUNE_NO_PRESCREEN = 16384,
-              VARIANT_PRUNE_NO_FEW = 32768, VARIANT_PRESCREEN_SCALAR = 65536;
+              VARIANT_PRUNE_NO_FEW = 32768, VARIANT_PRESCREEN_SCALAR = 65536, VARIANT_PRUNE_WHOLE_TILES = 262144;
+//   VARIANT_PRUNE_WHOLE_TILES (262144): the few-blocks path's wave tiles whole, never cut in halves / quarters while SIMDs idle (same bits)
 //   VARIANT_PRESCREEN_SCALAR (65536): phase 0 with one candidate per thread in scalar float32 (before the packed pairs; same bits)
 //   VARIANT_PRUNE_NO_FEW (32768): without its few-blocks path (K* once per block, wave-tile work items) when phase 0 leaves a handful
 //   VARIANT_PRUNE_NO_PRESCREEN (16384): its mean pass over every block, without the float32 pre-screen in front (phase 0)
@@ -647,6 +648,7 @@ hipError_t launch_sweep_timed(tgp_handle h, SweepArgs a, bool joint) {
         // the few-blocks path, chosen on the device when phase 0 leaves no more blocks than this: every one of them may
         // survive (the dump area), each has a K* slab of its own, and PRUNE_FEW_MAX is where the measurement stopped
         if (!(h->variant & VARIANT_PRUNE_NO_FEW)) pl.few_max = (int)std::min<int64_t>({PRUNE_FEW_MAX, pl.max_survivors, wg});
+        if (!(h->variant & VARIANT_PRUNE_WHOLE_TILES)) pl.tile_simds = 4 * h->num_cu;   // four SIMDs per compute unit
         words = PruneView::words(grid, pl.max_survivors, nb);
         // phase 0 reads what `update` left for THIS handle's model (a sweep over another handle's model does without)
         if (!(h->variant & (VARIANT_PRUNE_NO_SCREEN | VARIANT_PRUNE_NO_PRESCREEN)) && a.m.alpha == h->d_alpha.as<double>() &&

@@ -199,6 +199,7 @@ struct PruneLaunch {
   // the read-back of tgp_prescreen_means (null in the arg-max): per candidate the device's mean32 and its bound E
   double *m32_out, *e_out;
   int few_max;         // the few-blocks path: the cap on pre-listed blocks (0: off), <= PRUNE_FEW_MAX, max_survivors and the slabs
+  int tile_simds;      // its tile items are cut in halves / quarters while they leave SIMDs idle: the device's SIMDs (0: whole tiles)
 };
 // PruneLaunch::pre: |alpha|_1; the largest sqrt(SCALE) |Xs_k - Xs_0|_2 over the training rows; sqrt(SCALE) |Xs_0|_2;
 // sqrt(SCALE) itself

@@ -904,8 +904,9 @@ __global__ __launch_bounds__(1024) void prune_list_kernel(const SweepArgs a, con
 //   prune_kstar_kernel     generates the K* of pre-listed block p ONCE, into slab p, one k-step per work item;
 //   prune_mean_slab_kernel replays the mean's fma chain over the slab (same values, same order: same bits);
 //   prune_list_kernel      runs as ever;
-//   prune_tile_kernel      forms a survivor's row blocks one 64 x 32 wave tile per work item: every accumulator sees the fused
-//                          kernel's MFMAs in the fused order and goes to the dump word the split item writes;
+//   prune_tile_kernel      forms a survivor's row blocks one 64 x 32 wave tile per work item, or a half / a quarter of one while
+//                          the items leave SIMDs idle: every accumulator sees the fused kernel's MFMAs in the fused order and
+//                          goes to the dump word the split item writes;
 //   prune_fold_kernel      runs as ever.
 // prune_mean_kernel and the PRUNE sweep_dma_kernel return at once.  Every kernel has a fixed grid and reads P, S and the
 // flag from the header: no host synchronisation, no kernel waits for another.
@@ -1008,34 +1009,93 @@ __global__ __launch_bounds__(1024) void prune_mean_slab_kernel(const SweepArgs a
 // of lead before that wait, the others two and three.  Measured: SQ_WAIT_ANY is 9 % of the wave cycles at the headline
 // (profiles/r29_prune_tiles.txt).  Items are ordered longest row block first.
 constexpr int TILE_DEPTH = 4;
-__device__ __forceinline__ void tile_load(double (&av)[16], double (&bv)[8], const double* ap, const double* bp, int64_t Npad, int s) {
+// A PART of an item (FMN x FNN of the wave tile's 4 x 2 fragments, from fragment (fm0, fn0)): while whole items leave SIMDs
+// idle the launch is bound by its longest item -- row block nb - 1, wm = 3: 16 nb steps x 32 MFMAs x 64 cycles on one SIMD --
+// and a part has FMN FNN MFMAs per k4 round.  Cutting the OUTPUT tile leaves every accumulator its mfma_f64 sequence from
+// zero (same operands, same order, same skip rule) and its dump word: results keep their bits and prune_fold_kernel reads
+// what it read.  A part re-reads the operands its siblings read (a half 16 loads per step where the whole item has 24, a
+// quarter 12), so the kernel cuts only as far as the parts still fit the SIMDs side by side (prune_tile_kernel).
+template <int FMN, int FNN>
+__device__ __forceinline__ void tile_load(double (&av)[4 * FMN], double (&bv)[4 * FNN], const double* ap, const double* bp, int64_t Npad, int s) {
   const double* a0 = ap + (int64_t)s * DBK * Npad;
   const double* b0 = bp + (int64_t)s * DBK * DBN;
 #pragma unroll
   for (int k4 = 0; k4 < 4; ++k4) {
 #pragma unroll
-    for (int fm = 0; fm < 4; ++fm) av[k4 * 4 + fm] = a0[(int64_t)k4 * 4 * Npad + fm * 16];
+    for (int fm = 0; fm < FMN; ++fm) av[k4 * FMN + fm] = a0[(int64_t)k4 * 4 * Npad + fm * 16];
 #pragma unroll
-    for (int fn = 0; fn < 2; ++fn) bv[k4 * 2 + fn] = b0[k4 * 4 * DBN + fn * 16];
+    for (int fn = 0; fn < FNN; ++fn) bv[k4 * FNN + fn] = b0[k4 * 4 * DBN + fn * 16];
   }
 }
-__device__ __forceinline__ void tile_step(v4d (&acc)[4][2], const double (&av)[16], const double (&bv)[8]) {
+template <int FMN, int FNN>
+__device__ __forceinline__ void tile_step(v4d (&acc)[FMN][FNN], const double (&av)[4 * FMN], const double (&bv)[4 * FNN]) {
 #pragma unroll
   for (int k4 = 0; k4 < 4; ++k4)
 #pragma unroll
-    for (int fm = 0; fm < 4; ++fm)
+    for (int fm = 0; fm < FMN; ++fm)
 #pragma unroll
-      for (int fn = 0; fn < 2; ++fn) acc[fm][fn] = mfma_f64(av[k4 * 4 + fm], bv[k4 * 2 + fn], acc[fm][fn]);
+      for (int fn = 0; fn < FNN; ++fn) acc[fm][fn] = mfma_f64(av[k4 * FMN + fm], bv[k4 * FNN + fn], acc[fm][fn]);
 }
-__global__ __launch_bounds__(64) void prune_tile_kernel(const SweepArgs a) {
+// ap / bp: the lane's operand words of fragment (fm0, fn0) at step 0; dp: its dump word of accumulator (0, 0), register 0
+template <int FMN, int FNN>
+__device__ __forceinline__ void tile_part(const double* ap, const double* bp, int64_t Npad, int steps, int fm0, int fn0, double* dp) {
+  v4d acc[FMN][FNN];
+#pragma unroll
+  for (int i = 0; i < FMN; ++i)
+#pragma unroll
+    for (int j = 0; j < FNN; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
+  // (loads past the last step repeat it: in bounds, unused, and the loop body has no branch)
+  auto at = [&](int s) { return s < steps ? s : steps - 1; };
+  double av0[4 * FMN], bv0[4 * FNN], av1[4 * FMN], bv1[4 * FNN], av2[4 * FMN], bv2[4 * FNN], av3[4 * FMN], bv3[4 * FNN];
+  // The step count is a multiple of four: the loop body is four steps and one basic block.  The scheduling barriers keep
+  // every step's loads in front of the MFMAs they overlap (left alone, the compiler sinks them behind the MFMAs and waits
+  // for memory with nothing in flight).
+  tile_load<FMN, FNN>(av0, bv0, ap, bp, Npad, 0);
+  tile_load<FMN, FNN>(av1, bv1, ap, bp, Npad, 1);
+  tile_load<FMN, FNN>(av2, bv2, ap, bp, Npad, 2);
+  for (int s = 0; s < steps; s += TILE_DEPTH) {
+    tile_load<FMN, FNN>(av3, bv3, ap, bp, Npad, s + 3);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step<FMN, FNN>(acc, av0, bv0);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_load<FMN, FNN>(av0, bv0, ap, bp, Npad, at(s + 4));
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step<FMN, FNN>(acc, av1, bv1);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_load<FMN, FNN>(av1, bv1, ap, bp, Npad, at(s + 5));
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step<FMN, FNN>(acc, av2, bv2);
+    __builtin_amdgcn_sched_barrier(0);
+    tile_load<FMN, FNN>(av2, bv2, ap, bp, Npad, at(s + 6));
+    __builtin_amdgcn_sched_barrier(0);
+    tile_step<FMN, FNN>(acc, av3, bv3);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int fm = 0; fm < FMN; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < FNN; ++fn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dp[(((fm0 + fm) * 2 + fn0 + fn) * 4 + r) * 1024] = acc[fm][fn][r];
+}
+// The cut is decided here from S: quarters (one fm pair x one fn) while S nb 64 parts fit `simds`, halves (one fm
+// pair) while S nb 32 do, whole items otherwise -- once the items fill the SIMDs the phase is bound by throughput, and parts
+// would only read every B fragment again.  simds = 0 (tgp_set_variant bit 18): whole items.  The grid is fixed; blocks
+// past the parts exit.  Parts of an item are neighbours, items keep their order.
+__global__ __launch_bounds__(64) void prune_tile_kernel(const SweepArgs a, int simds) {
   if (!a.prune[PRUNE_W_FEW]) return;
   const int64_t Npad = a.m.Npad;
   const int nb = (int)(Npad / DBM);
   const int64_t S = (int64_t)a.prune[PRUNE_W_SURVIVORS];
-  if ((int64_t)blockIdx.x >= S * nb * 16) return;
+  const int64_t items = S * nb * 16;
+  const int cut = items * 4 <= (int64_t)simds ? 2 : items * 2 <= (int64_t)simds ? 1 : 0;
+  if ((int64_t)blockIdx.x >= (items << cut)) return;
   const int lane = threadIdx.x;
-  const int wt = (int)(blockIdx.x & 15u), wm = wt >> 2, wn = wt & 3;
-  const int64_t q = blockIdx.x >> 4;
+  const int part = (int)(blockIdx.x & ((1u << cut) - 1u));
+  const int fm0 = 2 * (part & 1), fn0 = part >> 1;
+  const int64_t item = blockIdx.x >> cut;
+  const int wt = (int)(item & 15), wm = wt >> 2, wn = wt & 3;
+  const int64_t q = item >> 4;
   const int srv = (int)(q % S), ib = nb - 1 - (int)(q / S);
   const int64_t nblk = (a.M + DBN - 1) / DBN;
   const PruneView pv{a.prune, nblk};
@@ -1044,48 +1104,13 @@ __global__ __launch_bounds__(64) void prune_tile_kernel(const SweepArgs a) {
   const int P = (int)a.prune[PRUNE_W_PRELISTED];
   const unsigned long long hit = __ballot(lane < P && pv.prelist()[lane < P ? lane : 0] == blk);
   const int p = __builtin_amdgcn_readfirstlane(hit ? __ffsll((long long)hit) - 1 : 0);
-  const double* ap = a.m.Wt + (int64_t)(lane >> 4) * Npad + (int64_t)ib * DBM + wm * 64 + (lane & 15);
-  const double* bp = a.kcache + (size_t)p * (size_t)Npad * DBN + (lane >> 4) * DBN + wn * 32 + (lane & 15);
+  const double* ap = a.m.Wt + (int64_t)(lane >> 4) * Npad + (int64_t)ib * DBM + wm * 64 + fm0 * 16 + (lane & 15);
+  const double* bp = a.kcache + (size_t)p * (size_t)Npad * DBN + (lane >> 4) * DBN + wn * 32 + fn0 * 16 + (lane & 15);
   const int steps = ib * DKSTEPS + wm * 4 + 4;
-  v4d acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
-  // (loads past the last step repeat it: in bounds, unused, and the loop body has no branch)
-  auto at = [&](int s) { return s < steps ? s : steps - 1; };
-  double av0[16], bv0[8], av1[16], bv1[8], av2[16], bv2[8], av3[16], bv3[8];
-  // The step count is a multiple of four: the loop body is four steps and one basic block.  The scheduling barriers keep
-  // every step's loads in front of the MFMAs they overlap (left alone, the compiler sinks them behind the MFMAs and waits
-  // for memory with nothing in flight).
-  tile_load(av0, bv0, ap, bp, Npad, 0);
-  tile_load(av1, bv1, ap, bp, Npad, 1);
-  tile_load(av2, bv2, ap, bp, Npad, 2);
-  for (int s = 0; s < steps; s += TILE_DEPTH) {
-    tile_load(av3, bv3, ap, bp, Npad, s + 3);
-    __builtin_amdgcn_sched_barrier(0);
-    tile_step(acc, av0, bv0);
-    __builtin_amdgcn_sched_barrier(0);
-    tile_load(av0, bv0, ap, bp, Npad, at(s + 4));
-    __builtin_amdgcn_sched_barrier(0);
-    tile_step(acc, av1, bv1);
-    __builtin_amdgcn_sched_barrier(0);
-    tile_load(av1, bv1, ap, bp, Npad, at(s + 5));
-    __builtin_amdgcn_sched_barrier(0);
-    tile_step(acc, av2, bv2);
-    __builtin_amdgcn_sched_barrier(0);
-    tile_load(av2, bv2, ap, bp, Npad, at(s + 6));
-    __builtin_amdgcn_sched_barrier(0);
-    tile_step(acc, av3, bv3);
-    __builtin_amdgcn_sched_barrier(0);
-  }
   double* dp = pv.dump(srv, ib, nb) + wt * 64 + lane;
-#pragma unroll
-  for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dp[((fm * 2 + fn) * 4 + r) * 1024] = acc[fm][fn][r];
+  if (cut == 2) tile_part<2, 1>(ap, bp, Npad, steps, fm0, fn0, dp);
+  else if (cut == 1) tile_part<2, 2>(ap, bp, Npad, steps, fm0, 0, dp);
+  else tile_part<4, 2>(ap, bp, Npad, steps, 0, 0, dp);
 }
 
 // Phase 3, one workgroup per split survivor: thread (wave, lane) replays fold_block over its dumped accumulators for
@@ -1174,7 +1199,10 @@ hipError_t TGP_CAT(launch_sweep_prune_kind, TGP_SWEEP_KIND)(hipStream_t s, const
   hipLaunchKernelGGL(prune_list_kernel, dim3(1), dim3(1024), 0, s, a, pl, (int)grid);
   e = launch_sweep_dma_dp<TGP_SWEEP_KIND, true>(s, a, grid);
   if (e != hipSuccess) return e;
-  if (pl.few_max > 0) hipLaunchKernelGGL(prune_tile_kernel, dim3((unsigned)(pl.few_max * nb * 16)), dim3(64), 0, s, a);
+  if (pl.few_max > 0) {   // whole items or halves of every pre-listed block, or the quarters that fit the SIMDs
+    const int64_t halves = (int64_t)pl.few_max * nb * 32, quarters = std::min<int64_t>(2 * halves, pl.tile_simds);
+    hipLaunchKernelGGL(prune_tile_kernel, dim3((unsigned)std::max(halves, quarters)), dim3(64), 0, s, a, pl.tile_simds);
+  }
   if (pl.max_survivors > 0) hipLaunchKernelGGL(prune_fold_kernel, dim3((unsigned)pl.max_survivors), dim3(1024), 0, s, a);
   return hipGetLastError();
 }
