@@ -479,6 +479,32 @@ int tgp_ivr_last_ms(tgp_handle h, double* posterior_ms, double* cross_ms, double
 int tgp_ivr_moments(tgp_handle h, const double* cov, const double* cross, const double* weights, int64_t G, int q, int64_t P,
                     double noise, double* reduction, int where);
 
+/* == PredictiveVariance / predictive_variance (acquisition/function/active_learning.py:36-110): the determinant of the joint
+ * predictive covariance of a batch of q points (D-optimal design).  A = cov + jitter ON EVERY ENTRY, as the reference adds the
+ * scalar to the whole matrix; A = L L^T in the tail kernel (tgp_kernels_pvar.hip; one wave per batch up to q = 16, one
+ * workgroup with the trailing updates on the matrix pipe above).  1 <= q <= TGP_PVAR_MAX_Q else TGP_ERR_SHAPE; jitter negative
+ * or not finite, G < 0 or a NULL array is TGP_ERR_ARG; G = 0 is a no-op.
+ *   det [G] = the product of the pivots L_ii^2 in order (= exp(logdet) to rounding; at q = 1 cov + jitter exactly), or
+ *     exp(logdet) itself for a batch whose running product left the normal range part-way;
+ *   logdet [G] = 2 sum_i log L_ii, may be NULL -- for batches whose determinant underflows;
+ *   gcov [G,q,q] = det A^-1, SYMMETRIC bit for bit, d det = sum_ij gcov_ij dcov_ij for every symmetric dcov (the convention of
+ *     tgp_qei_moments_grad and tgp_batch_ei_moments_grad: what tgp_joint_vjp takes).
+ * A batch whose factorisation meets a pivot that is not a positive finite number gets NaN in all its outputs and disturbs no other
+ * batch: there is NO TGP_ERR_NOT_PD here (an optimizer's stray batch must not end the call).  Float64, fixed summation orders,
+ * no atomics: identical calls return identical bits, and a batch's bits do not depend on the batches around it.
+ *   tgp_pvar_moments / tgp_pvar_moments_grad: the tail alone on caller-supplied covariances as the model returns them; needs no
+ *     data on the handle.  Chunks of 2^30 / (8 q^2) groups (with gcov: 2^28 / (8 q^2)).
+ *   tgp_pvar_values: Xq [G,q,d], any G: tgp_predict_joint's covariance of every chunk of 2^30 / (8 q^2) groups, then the tail;
+ *     bit for bit tgp_pvar_moments on tgp_predict_joint's covariance.  The time reported is the posterior part, as tgp_qei's.
+ *   tgp_pvar_value_grad: Xq [G,q,d] -> val [G] (bit for bit tgp_pvar_values' det), grad [G,q,d] = d val / d Xq:
+ *     tgp_joint_forward's arrays, the tail with gcov, and tgp_joint_vjp's second half with a zero mean adjoint on the same K*^T and
+ *     W K*, one synchronisation.  G * q <= 2048 else TGP_ERR_SHAPE. */
+#define TGP_PVAR_MAX_Q 64
+int tgp_pvar_moments(tgp_handle h, const double* cov, int64_t G, int q, double jitter, double* det, double* logdet, int where);
+int tgp_pvar_moments_grad(tgp_handle h, const double* cov, int64_t G, int q, double jitter, double* det, double* gcov, int where);
+int tgp_pvar_values(tgp_handle h, const double* Xq, int64_t G, int q, double jitter, double* det, double* logdet, int where);
+int tgp_pvar_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, double jitter, double* val, double* grad, int where);
+
 /* == value and gradient of a BATCH acquisition function at the handful of q-batches an L-BFGS-B iteration holds: the reference
  * optimises BatchMonteCarloExpectedImprovement through batchify_joint(generate_continuous_optimizer) (acquisition/optimizer.py:
  * 897-934, 344-560) with tfp.math.value_and_gradient (optimizer.py:628-629), i.e. autodiff THROUGH predict_joint

@@ -82,6 +82,10 @@ SIGNATURES = {
     "tgp_ivr_values": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int]),
     "tgp_ivr_last_ms": (C.c_int, [_vp, _dp, _dp, _dp]),
     "tgp_ivr_moments": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_double, _vp, C.c_int]),
+    "tgp_pvar_moments": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, _vp, _vp, C.c_int]),
+    "tgp_pvar_moments_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, _vp, _vp, C.c_int]),
+    "tgp_pvar_values": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, _vp, _vp, C.c_int]),
+    "tgp_pvar_value_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, _vp, _vp, C.c_int]),
     "tgp_traj_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_create_rff": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
     "tgp_traj_get_theta": (C.c_int, [_vp, _vp]),
@@ -176,6 +180,7 @@ NARROW_MAX_D = 32  # above it: float64 sweeps only (no int8 rungs), no trajector
 EHVI_MAX_P, EHVI_MAX_BOUNDS, EHVI_MAX_CELLS = 4, 512, 1 << 21  # limits of the tgp_ehvi_* calls (include/tgp.h)
 QEHVI_MAX_Q = 8  # points per batch of the tgp_qehvi_* calls (TGP_QEHVI_MAX_Q)
 IVR_MAX_Q, IVR_MAX_P = 16, 16384  # points per batch / integration points of the tgp_ivr_* calls (TGP_IVR_MAX_Q, TGP_IVR_MAX_P)
+PVAR_MAX_Q = 64  # points per batch of the tgp_pvar_* calls (TGP_PVAR_MAX_Q)
 
 
 def check(lib, handle, rc, group=False):

@@ -4,7 +4,11 @@ trieste/acquisition/function/active_learning.py:250-415 (Picheny et al. 2010).
 The reference evaluates ``model.conditional_predict_f(integration_points, additional_data=x)`` per candidate batch and
 averages.  Here the conditioned variance is the Schur complement over the q query points, everything that depends on
 (model, integration points) alone is built once on the device, and a candidate chunk costs the small-product posterior,
-one more product and a tail kernel (``trieste_amd.engine.ivr_values``; include/tgp.h tgp_ivr_values)."""
+one more product and a tail kernel (``trieste_amd.engine.ivr_values``; include/tgp.h tgp_ivr_values).
+
+And the batch criterion of D-optimal design, :class:`PredictiveVariance` (active_learning.py:36-110): the determinant of the
+joint predictive covariance of a batch, factorised on the device (``trieste_amd.engine.pvar_values``), with an opt-in
+gradient for the L-BFGS-B refinement of the batch."""
 from __future__ import annotations
 
 from typing import Optional
@@ -13,8 +17,92 @@ import numpy as np
 
 from .. import engine as _engine_mod
 from ..data import Dataset
+from ..sampler import JITTER
 from .function import _is_torch, _require_engine
 from .interface import AcquisitionFunctionClass, SingleModelAcquisitionBuilder
+
+
+class PredictiveVariance(SingleModelAcquisitionBuilder):
+    """Builder for the determinant of the predictive covariance matrix over the batch points (active_learning.py:36-83); for a
+    batch of one point the predictive variance.  ``differentiable=True`` builds the function with ``value_and_gradient``
+    (L-BFGS-B over the whole batch instead of a random search over batches); the default leaves it value-only."""
+
+    def __init__(self, jitter: float = JITTER, *, differentiable: bool = False):
+        """``jitter``: added to every entry of the covariance before its factorisation, as the reference adds it."""
+        if not 0.0 <= float(jitter) < np.inf:
+            raise ValueError(f"jitter must be finite and non-negative, got {jitter}")
+        self._jitter = jitter
+        self._differentiable = bool(differentiable)
+
+    def __repr__(self) -> str:
+        extra = ", differentiable=True" if self._differentiable else ""
+        return f"PredictiveVariance(jitter={self._jitter!r}{extra})"
+
+    def prepare_acquisition_function(self, model, dataset: Optional[Dataset] = None):
+        if not hasattr(model, "predict_joint"):
+            raise NotImplementedError(f"PredictiveVariance only works with models that support predict_joint; "
+                                      f"received {model!r}")
+        cls = differentiable_predictive_variance if self._differentiable else predictive_variance
+        return cls(model, self._jitter)
+
+    def update_acquisition_function(self, function, model, dataset: Optional[Dataset] = None):
+        return function  # no need to update anything
+
+
+class predictive_variance(AcquisitionFunctionClass):
+    """x [..., q, D] -> [..., 1]: det(cov + jitter) of the joint predictive covariance of the batch, the jitter added to every
+    entry as the reference does (active_learning.py:86-110); q = 1: the predictive variance.  Posterior, factorisation and
+    determinant run on the device (``trieste_amd.engine.pvar_values``; include/tgp.h tgp_pvar_values), 1 <= q <=
+    ``trieste_amd.engine.PVAR_MAX_Q``; a batch whose covariance is not positive definite gets NaN.  Value only:
+    ``batchify_joint`` sweeps it by random search; :class:`differentiable_predictive_variance` adds the gradient."""
+
+    def __init__(self, model, jitter: float):
+        if not hasattr(model, "predict_joint"):
+            raise NotImplementedError(f"PredictiveVariance only works with models that support predict_joint; "
+                                      f"received {model!r}")
+        self._model = model
+        self._engine = _require_engine(model, type(self).__name__)
+        self._jitter = float(jitter)
+
+    def _points(self, x):
+        if not _is_torch(x):
+            x = np.asarray(x, dtype=np.float64)
+        if len(x.shape) < 2:
+            raise ValueError(f"x must be [..., q, D], got shape {tuple(x.shape)}")
+        q = int(x.shape[-2])
+        if not 1 <= q <= _engine_mod.PVAR_MAX_Q:
+            raise ValueError(f"PredictiveVariance takes batches of 1 to {_engine_mod.PVAR_MAX_Q} points, got {q}")
+        return x
+
+    def __call__(self, x):
+        """x [..., q, D] -> [..., 1]."""
+        return _engine_mod.pvar_values(_require_engine(self._model, type(self).__name__), self._points(x), self._jitter)[..., None]
+
+    def log_det(self, x):
+        """x [..., q, D] -> [..., 1] = log det(cov + jitter), for batches whose determinant underflows."""
+        eng = _require_engine(self._model, type(self).__name__)
+        return _engine_mod.pvar_values(eng, self._points(x), self._jitter, with_logdet=True)[1][..., None]
+
+
+class differentiable_predictive_variance(predictive_variance):
+    """:class:`predictive_variance` with its gradient w.r.t. the batch, d det = det tr(A^-1 dA) through ``predict_joint``, in
+    one device call per chunk (``trieste_amd.engine.pvar_value_grad``).  Having ``value_and_gradient`` is what routes it to
+    the continuous optimizer."""
+
+    def value_and_gradient(self, points):
+        """points [P, q, D] -> (values [P], gradients [P, q, D])."""
+        x = np.ascontiguousarray(points.cpu().numpy() if _is_torch(points) else points, dtype=np.float64)
+        if x.ndim != 3:
+            raise ValueError(f"points must be [P, q, D], got shape {x.shape}")
+        x = self._points(x)
+        P, q, _ = x.shape
+        eng = _require_engine(self._model, type(self).__name__)
+        values, grads = np.empty(P), np.empty(x.shape)
+        chunk = max(1, getattr(eng, "JOINT_SMALL_POINTS", 2048) // q)
+        for g0 in range(0, P, chunk):
+            v, g = _engine_mod.pvar_value_grad(eng, x[g0:g0 + chunk], self._jitter)
+            values[g0:g0 + chunk], grads[g0:g0 + chunk] = np.asarray(v), np.asarray(g)
+        return values, grads
 
 
 class IntegratedVarianceReduction(SingleModelAcquisitionBuilder):

@@ -2584,7 +2584,8 @@ struct MomentArray {
   int64_t n;
   double* dev;   // where the tail finds the chunk's groups (stage_chunk)
 };
-enum { M_MEAN, M_COV, M_VAL, M_GMEAN, M_GCOV, M_ARRAYS, M_SAMPLES = M_GCOV };   // (the samples take the idle adjoint's place)
+enum { M_MEAN, M_COV, M_VAL, M_GMEAN, M_GCOV, M_ARRAYS, M_SAMPLES = M_GCOV, M_LOGDET = M_GMEAN };   // (the samples and the
+// predictive variance's second value [G] take an idle adjoint's place)
 using MomentArrays = std::array<MomentArray, M_ARRAYS>;
 // mean [obj][G][nm], cov [obj][G][nc] -> val [G], and with adjoints gmean, gcov in the inputs' shapes
 MomentArrays moment_arrays(tgp_handle h, int obj, int64_t nm, int64_t nc, const double* mean, const double* cov, double* val,
@@ -2990,6 +2991,79 @@ int tgp_ivr_moments(tgp_handle h, const double* cov, const double* cross, const 
       launch_ivr_tail(h->stream, a, gc);
     });
   });
+}
+
+// ---- predictive variance (tgp_kernels_pvar.hip): det(cov + jitter) of every q-batch ----------------------------------------------
+// The tail writes NaN for a batch that is not positive definite and leaves d_info alone, so the chunk loop's breakdown report
+// never fires for these entries; the message is what it would say if a later tail did report.
+constexpr const char* PVAR_NOT_PD = "predictive variance: cov + jitter of group %lld is not positive definite";
+
+static int pvar_check(tgp_handle h, int64_t G, int q, double jitter) {
+  if (q < 1 || q > PVAR_MAX_Q) return fail(h, TGP_ERR_SHAPE, "predictive variance: q must be in 1..%d, got %d", PVAR_MAX_Q, q);
+  if (!(jitter >= 0.0 && jitter < HUGE_VAL)) return fail(h, TGP_ERR_ARG, "jitter must be finite and >= 0");
+  if (G < 0) return fail(h, TGP_ERR_ARG, "bad arguments");
+  return TGP_OK;
+}
+
+int tgp_pvar_moments(tgp_handle h, const double* cov, int64_t G, int q, double jitter, double* det, double* logdet, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = pvar_check(h, G, q, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!cov || !det) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  MomentArrays m = moment_arrays(h, 1, q, (int64_t)q * q, nullptr, cov, det);
+  m[M_LOGDET] = {logdet, false, &h->s_in, 1, 1, nullptr};   // optional, [G]
+  return moments_chunks(h, G, joint_group_chunk(q), PVAR_NOT_PD, where, m, [&](int64_t gc, int64_t) {
+    return bracketed(h, [&] { launch_pvar_tail(h->stream, m[M_COV].dev, gc, q, jitter, m[M_VAL].dev, m[M_LOGDET].dev, nullptr, nullptr); });
+  });
+}
+
+int tgp_pvar_moments_grad(tgp_handle h, const double* cov, int64_t G, int q, double jitter, double* det, double* gcov, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = pvar_check(h, G, q, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!cov || !det || !gcov) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  MomentArrays m = moment_arrays(h, 1, q, (int64_t)q * q, nullptr, cov, det, nullptr, gcov);
+  // (covariances and adjoints of a chunk within 256 MiB each)
+  return moments_chunks(h, G, groups_within(1ull << 28, (int64_t)q * q), PVAR_NOT_PD, where, m, [&](int64_t gc, int64_t) {
+    return bracketed(h, [&] { launch_pvar_tail(h->stream, m[M_COV].dev, gc, q, jitter, m[M_VAL].dev, nullptr, nullptr, m[M_GCOV].dev); });
+  });
+}
+
+int tgp_pvar_values(tgp_handle h, const double* Xq, int64_t G, int q, double jitter, double* det, double* logdet, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = pvar_check(h, G, q, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!Xq || !det) return fail(h, TGP_ERR_ARG, "bad arguments");
+  if (int rc = set_device(h)) return rc;
+  // tgp_qei's body with two outputs per group: under host residency det and logdet of a chunk share s_out3
+  return for_group_chunks(h, G, joint_group_chunk(q), true, PVAR_NOT_PD, [&](int64_t g0, int64_t gc) -> int {
+    const double* dXq;
+    double *dmean, *dcov, *ddet;
+    if (int rc = joint_common(h, Xq + g0 * q * h->d, gc, q, where, &dXq, &dmean, &dcov, nullptr, nullptr, true)) return rc;
+    if (int rc = stage_out_prepare(h, h->s_out3, det + g0, (size_t)2 * gc, where, &ddet)) return rc;
+    double* const dlog = !logdet ? nullptr : where == TGP_DEVICE ? logdet + g0 : ddet + gc;
+    launch_pvar_tail(h->stream, dcov, gc, q, jitter, ddet, dlog, nullptr, nullptr);
+    if (int rc = stage_out_finish(h, ddet, det + g0, (size_t)gc, where)) return rc;
+    return stage_out_finish(h, dlog, logdet ? logdet + g0 : nullptr, (size_t)gc, where);
+  });
+}
+
+// K*^T, W K*, Gram product, pick, the tail with the covariance's adjoint (the mean's is zero), mix, the A product,
+// joint_vjp_tail: one synchronisation.
+int tgp_pvar_value_grad(tgp_handle h, const double* Xq, int64_t G, int q, double jitter, double* val, double* grad, int where) {
+  if (!h) return TGP_ERR_ARG;
+  if (int rc = pvar_check(h, G, q, jitter)) return rc;
+  if (G == 0) return TGP_OK;
+  if (!val || !grad) return fail(h, TGP_ERR_ARG, "val / grad is NULL");
+  const double* dXq;
+  int64_t P, Ppad;
+  if (int rc = joint_small_common(h, Xq, G, q, where, &dXq, &P, &Ppad)) return rc;
+  return joint_value_grad(h, dXq, G, q, P, Ppad, val, grad, where, PVAR_NOT_PD,
+                          [&](const double*, const double* dcov, double* dval, double* dgm, double* dgc) {
+                            launch_pvar_tail(h->stream, dcov, G, q, jitter, dval, nullptr, dgm, dgc);
+                          });
 }
 
 // ---- trajectories -----------------------------------------------------------------------------

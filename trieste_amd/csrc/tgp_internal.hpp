@@ -378,6 +378,13 @@ size_t ivr_tail_lds_bytes(int q, int d, bool given);
 void launch_ivr_tail(hipStream_t s, const IvrTailArgs& a, int64_t G);
 void launch_ivr_scale_z(hipStream_t s, const double* Z, const double* ls, int64_t P, int d, int64_t ldz, double* Zt);
 void launch_ivr_c0(hipStream_t s, const double* w, const double* var, int64_t P, double* c0);
+// predictive variance (tgp_kernels_pvar.hip): det / logdet [G] of cov [G][q][q] + jitter on every entry, 1 <= q <= PVAR_MAX_Q;
+// logdet may be null; gcov [G][q][q] = det (cov + jitter)^-1 (null: value only), gmean [G][q] zeroed with it (or null).  A batch
+// that is not positive definite gets NaN, nothing is reported.  q <= PVAR_WAVE_Q: one wave per batch; above: one workgroup.
+constexpr int PVAR_MAX_Q = 64, PVAR_WAVE_Q = 16;
+size_t pvar_tail_lds_bytes(int q, bool grad);
+void launch_pvar_tail(hipStream_t s, const double* cov, int64_t G, int q, double jitter, double* det, double* logdet,
+                      double* gmean, double* gcov);
 // gradients (tgp_kernels_grad.hip)
 void launch_kstar_t(hipStream_t s, const ModelDev& m, const double* Xq, int64_t P, int64_t Ppad, double* B);
 size_t predict_small_scratch_doubles(int64_t Ppad);   // `part` of launch_predict_small_tail

@@ -912,6 +912,86 @@ def ivr_moments(engine, cov, cross, weights=None, noise: float = 0.0):
     return out
 
 
+PVAR_MAX_Q = _lib.PVAR_MAX_Q
+
+
+def _pvar_args(q: int, jitter: float) -> float:
+    if not 1 <= q <= PVAR_MAX_Q:
+        raise ValueError(f"the predictive variance takes 1 <= q <= {PVAR_MAX_Q} points per batch, got {q}")
+    jitter = float(jitter)
+    if not 0.0 <= jitter < np.inf:
+        raise ValueError(f"jitter must be finite and non-negative, got {jitter}")
+    return jitter
+
+
+def _pvar_cov(cov) -> _Arg:
+    c = _Arg(cov)
+    if len(c.shape) < 2 or c.shape[-1] != c.shape[-2]:
+        raise ValueError(f"cov must be [..., q, q], got {c.shape}")
+    return c
+
+
+def pvar_moments(engine, cov, jitter: float = 1e-6, with_logdet: bool = False):
+    """The predictive-variance tail on caller-supplied covariances: cov [..., q, q] as a model's ``predict_joint`` returns them
+    (1 <= q <= ``PVAR_MAX_Q``) -> det(cov + jitter) [...], the jitter added to EVERY entry as the reference does;
+    ``with_logdet=True`` -> (det, logdet), for batches whose determinant underflows (tgp_pvar_moments).  A batch that is not
+    positive definite gets NaN.  Needs no data on the engine."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "pvar_moments"):
+        return engine.pvar_moments(cov, jitter, with_logdet)
+    c = _pvar_cov(cov)
+    lead, q = c.shape[:-2], c.shape[-1]
+    jitter = _pvar_args(q, jitter)
+    det, pd = GPEngine._out(c, lead)
+    logdet, pl = GPEngine._out(c, lead) if with_logdet else (None, None)
+    engine._chk(engine._lib.tgp_pvar_moments(engine._h, c.ptr, _groups(lead), q, jitter, pd, pl, c.where))
+    return (det, logdet) if with_logdet else det
+
+
+def pvar_moments_grad(engine, cov, jitter: float = 1e-6):
+    """The tail with its adjoint: cov [G, q, q] -> (det [G], gcov [G, q, q] = det (cov + jitter)^-1), gcov symmetric bit for
+    bit, d det = sum gcov * dcov for every symmetric dcov (tgp_pvar_moments_grad).  Needs no data on the engine."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "pvar_moments_grad"):
+        return engine.pvar_moments_grad(cov, jitter)
+    c = _pvar_cov(cov)
+    if len(c.shape) != 3:
+        raise ValueError(f"cov must be [G, q, q], got {c.shape}")
+    G, q = c.shape[0], c.shape[1]
+    jitter = _pvar_args(q, jitter)
+    det, pd = GPEngine._out(c, (G,))
+    gcov, pg = GPEngine._out(c, c.shape)
+    engine._chk(engine._lib.tgp_pvar_moments_grad(engine._h, c.ptr, G, q, jitter, pd, pg, c.where))
+    return det, gcov
+
+
+def pvar_values(engine, Xq, jitter: float = 1e-6, with_logdet: bool = False):
+    """Xq [..., q, d] (1 <= q <= ``PVAR_MAX_Q``) -> [...]: the determinant of the joint predictive covariance of every q-batch,
+    posterior and tail on the device (tgp_pvar_values; the reference's ``predictive_variance.__call__``);
+    ``with_logdet=True`` -> (det, logdet).  Bit for bit :func:`pvar_moments` on ``predict_joint``'s covariance."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "pvar_values"):
+        return engine.pvar_values(Xq, jitter, with_logdet)
+    a, lead, q, G = _batch_points(engine.d, Xq)
+    jitter = _pvar_args(q, jitter)
+    det, pd = GPEngine._out(a, lead)
+    logdet, pl = GPEngine._out(a, lead) if with_logdet else (None, None)
+    engine._chk(engine._lib.tgp_pvar_values(engine._h, a.ptr, G, q, jitter, pd, pl, a.where))
+    return (det, logdet) if with_logdet else det
+
+
+def pvar_value_grad(engine, Xq, jitter: float = 1e-6):
+    """Xq [G, q, d] (1 <= q <= ``PVAR_MAX_Q``, G * q <= 2048) -> (det [G], its gradient [G, q, d]) in one device call: the
+    joint posterior, the tail with the covariance's adjoint and the posterior's vector-Jacobian product
+    (tgp_pvar_value_grad).  The value is bit for bit :func:`pvar_values`'."""
+    if not isinstance(engine, GPEngine) and hasattr(engine, "pvar_value_grad"):
+        return engine.pvar_value_grad(Xq, jitter)
+    a, G, q = engine._joint_small(Xq)
+    jitter = _pvar_args(q, jitter)
+    val, pv = GPEngine._out(a, (G,))
+    grad, pg = GPEngine._out(a, (G, q, engine.d))
+    if G:
+        engine._chk(engine._lib.tgp_pvar_value_grad(engine._h, a.ptr, G, q, jitter, pv, pg, a.where))
+    return val, grad
+
+
 def _qei_moment_args(mean, cov, eps):
     (m, c), e = _moment_pair(mean, cov, "G", same_place=False), _Arg(eps)
     G, q = m.shape
