@@ -489,6 +489,9 @@ int tgp_ivr_moments(tgp_handle h, const double* cov, const double* cross, const 
  *   logdet [G] = 2 sum_i log L_ii, may be NULL -- for batches whose determinant underflows;
  *   gcov [G,q,q] = det A^-1, SYMMETRIC bit for bit, d det = sum_ij gcov_ij dcov_ij for every symmetric dcov (the convention of
  *     tgp_qei_moments_grad and tgp_batch_ei_moments_grad: what tgp_joint_vjp takes).
+ * Of cov the LOWER TRIANGLE AND THE DIAGONAL are read; what stands above the diagonal, NaN included, changes no bit of any output.
+ * A determinant outside float64's range comes back as 0 or inf (a subnormal one to within one subnormal spacing) with logdet still
+ * right; gcov of a batch whose det is not a normal number is unspecified.
  * A batch whose factorisation meets a pivot that is not a positive finite number gets NaN in all its outputs and disturbs no other
  * batch: there is NO TGP_ERR_NOT_PD here (an optimizer's stray batch must not end the call).  Float64, fixed summation orders,
  * no atomics: identical calls return identical bits, and a batch's bits do not depend on the batches around it.
